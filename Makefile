@@ -3,7 +3,8 @@
 # gpurun on this pool).
 PY ?= python
 
-.PHONY: all build test test-gpu check lint sanitize bench bench-all prof clean
+.PHONY: all build test test-gpu check lint sanitize bench bench-full \
+	bench-all prof clean
 
 all: build
 
@@ -24,12 +25,16 @@ lint:
 sanitize:                 ## host codec suites under ASan + UBSan
 	bash tools/sanitize_host.sh
 
-bench:                    ## headline benchmark, 1 GPU
+bench:                    ## headline benchmark, 1 GPU (timed steps only)
 	$(PY) bench.py
 
+bench-full:               ## + round trips, bulk TCP, sustained window
+	$(PY) bench.py --full
+
 bench-all:                ## gpu tests + get / mix / storm workloads (needs a GPU)
-	bash tools/gpu.sh tests bench=--no-rtt bench=--no-rtt,--workload,mix \
-	  bench=--no-rtt,--workload,storm
+	bash tools/gpu.sh tests bench=--full,--no-rtt \
+	  bench=--full,--no-rtt,--workload,mix \
+	  bench=--full,--no-rtt,--workload,storm
 
 prof:                     ## rocprofv3 kernel stats for the three workloads
 	bash tools/gpu.sh prof=prof,get,mix,storm

@@ -55,6 +55,17 @@ helps.  ``p50_get_rtt_us_evloop`` is the same round trip
 through the callback API on the client's event loop (one get issued from
 the previous one's callback), the way the single-threaded reference runs
 ``get(path, cb)``.
+
+A plain run (``--gpus 1 --steps N --warmup W``) does what the headline needs
+and nothing else: build the tree and the pipeline, W warm-up steps, N timed
+steps (every reply checked on the device), the result line.  ``--full`` adds
+what the paragraphs above describe besides that: the round trips and the
+bulk-TCP figures (the servers start before the GPU is touched), the ~1 s
+``sustained`` window and the comparison run of the other GET mode; their
+fields of the result line are null without it.  ``--dump-outputs DIR``
+writes the replies of the last timed step as ``DIR/<name>.npy`` (see
+``dump_outputs``); the tree, the requests and so the replies are the same
+for the same arguments.
 """
 
 import argparse
@@ -76,6 +87,10 @@ sys.path.insert(0, ROOT)
 # reference's own ZKDecodeStream frame+decode on one Xeon core, best case
 # 0.51 M packets/s.  The reference publishes no headline number.
 REF_PKTS_PER_S = 0.51e6
+
+# ctime / mtime of the synthetic tree's static nodes: a constant, so the same
+# arguments give the same tree (and the same replies) from run to run
+TREE_CTIME_MS = 1_700_000_000_000
 
 
 def start_rtt_server():
@@ -352,14 +367,20 @@ def run_ensemble(a):
         if dev is not None:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        got = 0
-        for _ in range(a.steps):
-            got += wl.step()
+        per_step = [wl.step() for _ in range(a.steps)]
+        got = sum(per_step)
         if world > 1:
             dist.barrier()
         if dev is not None:
             torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if a.dump_outputs:
+            # the events this rank received in each timed step
+            import numpy as np
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, '%sdeliveries.npy' % (
+                'rank%d_' % rank if world > 1 else '')),
+                np.asarray(per_step, np.float64))
         bad = wl.verify()
         stats = torch.tensor([elapsed * 1e6, got, 1 if bad else 0,
                               wl.failovers, wl.rearmed(),
@@ -427,8 +448,21 @@ def main():
     ap.add_argument('--name-pad', default=None,
                     help='LO-HI: leaf names padded by a uniform LO..HI '
                          'characters (variable path lengths)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else '
+                         'the benchmark measures: the interactive RTT and '
+                         'bulk-TCP runs, the ~1 s sustained window and, for '
+                         'get at N > 1 or with --force-route, the comparison '
+                         'run of the other GET mode (a plain run times the '
+                         'steps and prints the result line, these fields '
+                         'null)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed '
+                         'step computed (the decoded reply tables a caller '
+                         'of the pipeline receives, a fixed seeded sample of '
+                         'them when they are large) as DIR/<name>.npy')
     ap.add_argument('--no-rtt', action='store_true',
-                    help='skip the interactive RTT and bulk-TCP runs')
+                    help='--full: skip the interactive RTT and bulk-TCP runs')
     ap.add_argument('--bulk-batch', type=int, default=1 << 20,
                     help='requests per Client.bulk_get batch of the '
                          'bulk-TCP measurement')
@@ -479,9 +513,10 @@ def main():
                          'all_to_all_single on HBM tensors, captured in the '
                          'HIP graph) and compare it with the local pipeline')
     ap.add_argument('--no-sustain', action='store_true',
-                    help='skip the second, ~1 s timed window')
+                    help='--full: skip the second, ~1 s timed window')
     ap.add_argument('--no-compare', action='store_true',
-                    help='get, N > 1: skip the replica comparison run')
+                    help='--full, get, N > 1: skip the replica comparison '
+                         'run')
     ap.add_argument('--paths', type=int, default=65536,
                     help='ensemble: watched znodes (one owner rank each)')
     ap.add_argument('--writes', type=int, default=4096,
@@ -491,6 +526,9 @@ def main():
                          'is on and makes that step\'s writes during the '
                          'outage (replayed through SET_WATCHES)')
     a = ap.parse_args()
+    if not a.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        a.no_rtt = a.no_sustain = a.no_compare = True
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return launch(a)
     # a rank that fails (tests inject one with ZKMI_BENCH_FAIL_RANK) ends
@@ -627,6 +665,95 @@ def _reduce(elapsed, ok_total, world, cdev):
     return el.item(), int(ok.item())
 
 
+DUMP_BUDGET = 48 << 20      # bytes of .npy a dump may write (all files)
+DUMP_ROWS = 1 << 16         # replies sampled per connection
+
+
+def _last_replies(pipe):
+    """(reply tables, reply byte stream or None) of the last step of every
+    connection of ``pipe`` (the pipelines keep them in ``last``)."""
+    from zkmi.ops.batch import ReplyBatch
+    out = []
+    for c in getattr(pipe, 'subs', None) or [pipe]:
+        last = getattr(c, 'last', None) or ()
+        rep = next((x for x in last if isinstance(x, ReplyBatch)), None)
+        if rep is None:
+            continue
+        rx = next((x for x in last if isinstance(x, torch.Tensor) and
+                   x.dtype == torch.uint8), None)
+        out.append((rep, rx))
+    return out
+
+
+def dump_outputs(dirname, pipe, ok_total, a, rank, world):
+    """``--dump-outputs``: what the last timed step handed its caller, as
+    ``<name>.npy`` (float64; payload bytes float32) under ``dirname``.
+
+    ``checked_ok``: the replies the on-device check accepted over the timed
+    steps.  Per connection k of the step (``connK_*``): ``count`` (replies
+    decoded) and, for a fixed seeded sample of ``DUMP_ROWS`` replies (``row``:
+    their positions in the reply stream, ascending), the decoded reply table
+    columns ``xid err opcode status pay_len aux0 aux1``.  The get workload
+    reads a tree that no step changes, so every value of its replies repeats
+    from run to run and it also dumps ``pay_off``, the Stat columns
+    (``zkmi.ops.batch.STAT64`` / ``STAT32`` names) and ``payload`` (the
+    data bytes of the first sampled replies, one row each, -1 past a
+    reply's length).  The write workloads hand out zxids and node slots with
+    atomics (their order differs between runs) and stamp the wall clock, so
+    those columns stay out; so does the reply header's ``zxid`` everywhere
+    (the server's counter when it served the batch: the connections of a
+    step share the tree and run side by side).  With more than one rank the
+    names start with ``rankR_``."""
+    import numpy as np
+    from zkmi.ops.batch import STAT64, STAT32
+    os.makedirs(dirname, exist_ok=True)
+    pre = 'rank%d_' % rank if world > 1 else ''
+
+    def save(name, t, dtype=torch.float64):
+        np.save(os.path.join(dirname, pre + name + '.npy'),
+                t.detach().to('cpu', dtype).numpy())
+    torch.cuda.synchronize()
+    save('checked_ok', ok_total.sum().view(1))
+    conns = _last_replies(pipe)
+    budget = DUMP_BUDGET // max(len(conns), 1)
+    static = a.workload == 'get'
+    cols = ['xid', 'err', 'opcode', 'status', 'pay_len', 'aux0', 'aux1']
+    if static:
+        cols += ['pay_off']
+    for k, (rep, rx) in enumerate(conns):
+        c = 'conn%d_' % k
+        n = min(int(rep.count.view(-1)[0].item()), rep.xid.numel())
+        save(c + 'count', rep.count.view(-1)[:1])
+        # 8 bytes a value, the columns above + row + 11 Stat columns
+        rows = min(n, DUMP_ROWS, budget // 2 // (8 * 24))
+        g = torch.Generator()
+        g.manual_seed(k)
+        pick = torch.randperm(n, generator=g)[:rows].sort().values \
+            if rows < n else torch.arange(n)
+        pick = pick.to(rep.xid.device)
+        save(c + 'row', pick)
+        for f in cols:
+            save(c + f, getattr(rep, f)[pick])
+        if not static:
+            continue
+        for i, f in enumerate(STAT64):
+            save(c + f, rep.stat64[i][pick])
+        for i, f in enumerate(STAT32):
+            save(c + f, rep.stat32[i][pick])
+        if rx is None or rows == 0:
+            continue
+        ln = rep.pay_len[pick].long().clamp_(0, 1 << 20)
+        off = rep.pay_off[pick]
+        ln[off < 0] = 0
+        w = max(int(ln.max().item()), 1)
+        prow = min(rows, max(budget // 2 // (4 * w), 1))
+        col = torch.arange(w, device=rx.device)
+        pos = (off[:prow, None] + col[None, :]).clamp_(0, rx.numel() - 1)
+        pay = torch.where(col[None, :] < ln[:prow, None], rx[pos].float(),
+                          torch.tensor(-1.0, device=rx.device))
+        save(c + 'payload', pay, torch.float32)
+
+
 def run_rank(a):
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -682,7 +809,8 @@ def run_rank(a):
     def make_get(replica):
         if replica:
             tree = S.GpuTree(a.nodes, a.data_bytes, device=dev, seed=rank,
-                             data_dist=dd, name_pad=npad)
+                             data_dist=dd, name_pad=npad,
+                             ctime_ms=TREE_CTIME_MS)
             return S.GetPipeline(tree, a.batch, seed=rank, streams=a.streams,
                                  stagger=a.stagger,
                                  priority=a.stream_priority)
@@ -690,7 +818,8 @@ def run_rank(a):
         # every rank holds the same layout and data (seed 0); its index
         # covers only the leaves whose path hashes to it
         tree = S.GpuTree(a.nodes, a.data_bytes, device=dev, seed=0,
-                         data_dist=dd, name_pad=npad, shard=(rank, world))
+                         data_dist=dd, name_pad=npad, shard=(rank, world),
+                         ctime_ms=TREE_CTIME_MS)
         return ShardedGetPipeline(tree, a.batch, seed=rank, coll_device=cdev,
                                   streams=a.streams,
                                   force_route=a.force_route)
@@ -700,7 +829,7 @@ def run_rank(a):
         per_step = a.batch
     elif a.workload == 'watch':
         tree = S.GpuTree(a.nodes, a.data_bytes, device=dev, seed=rank,
-                         watch_cap=2 * a.batch)
+                         watch_cap=2 * a.batch, ctime_ms=TREE_CTIME_MS)
         pipe = S.WatchPipeline(tree, a.batch, seed=rank,
                                coll_device=cdev if world > 1 else None)
         # write-triggered notifications decoded per rank (every rank's
@@ -725,7 +854,8 @@ def run_rank(a):
                              32 if a.workload in ('storm', 'mix') else
                              16 if a.workload in ('chain', 'nest')
                              else 2),
-                         compact_free=a.workload in ('mix', 'nest'))
+                         compact_free=a.workload in ('mix', 'nest'),
+                         ctime_ms=TREE_CTIME_MS)
         if a.workload == 'chain':
             pipe = S.ChainPipeline(tree, a.batch, a.data_bytes, seed=rank)
             per_step = pipe.n
@@ -758,6 +888,9 @@ def run_rank(a):
     elapsed, ok_total, a.graph = _time_steps(pipe, a, world, dev)
     elapsed = checked(pipe, elapsed, ok_total)
     value = ops / elapsed
+    if a.dump_outputs:
+        # before anything below runs the pipeline again
+        dump_outputs(a.dump_outputs, pipe, ok_total, a, rank, world)
     sustained = None
     if not a.no_sustain:
         # (elapsed is the max over ranks: every rank runs the same count)

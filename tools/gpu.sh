@@ -55,7 +55,8 @@ for step in "$@"; do
       for w in ${@:-get}; do
         (cd /tmp && run 300 $OUT/${n}_${tag}_$w.log rocprofv3 --kernel-trace \
           --stats --output-format csv -d $OUT/${tag}_$w -o prof -- \
-          python3 $R/bench.py --workload $w --steps 5 --warmup 1 --no-rtt) \
+          python3 $R/bench.py --full --workload $w --steps 5 --warmup 1 \
+          --no-rtt) \
           || { rc=$?; break; }
       done
       [ $rc -eq 0 ] ;;

@@ -10,7 +10,7 @@ OUT=gpurun_out/ab_${AB_TAG:-args}.log
 : > $OUT
 for i in $(seq ${ROUNDS:-2}); do
   for set in $AB_ARGS; do
-    timeout -k 10 300 python bench.py --no-rtt $(echo "$set" | tr ',' ' ') \
+    timeout -k 10 300 python bench.py --full --no-rtt $(echo "$set" | tr ',' ' ') \
       > gpurun_out/ab_run.log 2>&1 || { tail -20 gpurun_out/ab_run.log; exit 1; }
     python - "$set" gpurun_out/ab_run.log >> $OUT <<'PY'
 import json, sys

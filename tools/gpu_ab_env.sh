@@ -22,7 +22,7 @@ for i in $(seq ${ROUNDS:-3}); do
   for set in $SETS; do
     envs=""
     [ "$set" != "-" ] && envs=$(echo "$set" | tr ',' ' ')
-    env $envs timeout -k 10 300 python bench.py --no-rtt ${BENCH_ARGS:-} \
+    env $envs timeout -k 10 300 python bench.py --full --no-rtt ${BENCH_ARGS:-} \
       > gpurun_out/ab_run.log 2>&1 || { tail -20 gpurun_out/ab_run.log; exit 1; }
     python - "$set" gpurun_out/ab_run.log >> $OUT <<'PY'
 import json, sys

@@ -27,8 +27,9 @@ trun() {      # torchrun starts them (the driver's form)
   echo "$tag rc=$rc $(grep -h '^{' $OUT/$tag.log | tail -1 | cut -c1-400)"
   return $rc
 }
-own 2 get2_own --no-rtt --batch $B && trun 2 get2_torchrun --no-rtt --batch $B && \
-  own 2 get2_sharded --no-rtt --batch $B --sharded && \
-  own 8 get8_own --no-rtt --batch $B && \
-  own 2 storm2 --no-rtt --workload storm --batch 65536 && \
+own 2 get2_own --full --no-rtt --batch $B && \
+  trun 2 get2_torchrun --full --no-rtt --batch $B && \
+  own 2 get2_sharded --full --no-rtt --batch $B --sharded && \
+  own 8 get8_own --full --no-rtt --batch $B && \
+  own 2 storm2 --full --no-rtt --workload storm --batch 65536 && \
   own 4 ens4 --workload ensemble
