@@ -276,6 +276,16 @@ int zk_tree_seq_order(const ZkTree*, const uint8_t*, const int64_t*,
 // data), out[1] = live nodes, out[2] = hash entries in use (live +
 // tombstones), out[3] = tombstones
 int zk_tree_digest(const ZkTree*, unsigned long long*, hipStream_t);
+// GET_CHILDREN / GET_CHILDREN2 batches from the tree (tree.hip list_*):
+// bytes of the workspace for ncap requests, and the serve itself (frames,
+// count, ncap, watcher slot, max reply frame, want[node cap] int32 idling at
+// 0x7fffffff, workspace + bytes, out + capacity, rec_off[ncap], total, err,
+// terminate)
+int64_t zk_tree_list_workspace(int64_t ncap);
+int zk_tree_list(const ZkTree*, const uint8_t*, const int64_t*,
+                 const int32_t*, const int64_t*, int64_t, int32_t, int64_t,
+                 int32_t*, uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
+                 int64_t*, int32_t*, int32_t, hipStream_t);
 int zk_bench_gen_get(int64_t, uint64_t, int64_t, int64_t, int32_t,
                      const int64_t*, int64_t*, int32_t*, int64_t*, int32_t*,
                      const int64_t*, int64_t*, int64_t*, hipStream_t);

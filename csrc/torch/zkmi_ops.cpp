@@ -854,6 +854,45 @@ void tree_digest(const std::vector<Tensor>& t, const Tensor& out) {
          "tree_digest");
 }
 
+// GET_CHILDREN / GET_CHILDREN2 batches served from the tree (tree.hip
+// list_*): workspace bytes for ncap requests, then per batch the request
+// frames -> the framed replies in out[:total], their starts in rec_off.
+// want: int32 per node slot, all 0x7fffffff (the kernels leave it so).
+int64_t tree_list_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_list_workspace n");
+  return zk_tree_list_workspace(n);
+}
+
+void tree_list(const std::vector<Tensor>& t, const Tensor& rx,
+               const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
+               int64_t ncap, int64_t wslot, int64_t max_frame,
+               const Tensor& want, const Tensor& ws, const Tensor& out,
+               int64_t out_cap, const Tensor& rec_off, const Tensor& total,
+               const Tensor& err, bool terminate) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  TORCH_CHECK(wslot >= -1 && wslot < 64, "zkmi: watcher slot -1..63");
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: tree_list ncap");
+  TORCH_CHECK(max_frame >= 0, "zkmi: tree_list max_frame");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_list out_cap");
+  uint8_t* w = P<uint8_t>(ws, U8, zk_tree_list_workspace(ncap),
+                          "list workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w) % 16 == 0,
+              "zkmi: list workspace must be 16-byte aligned");
+  hip_ok(zk_tree_list(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, (int32_t)wslot,
+             max_frame, P<int32_t>(want, I32, s.store.cap, "want", d), w,
+             ws.numel(), P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_list");
+}
+
 void tree_expire(const std::vector<Tensor>& t, int64_t session, int64_t ncap,
                  const Tensor& removed) {
   ZkTree s = tree(t);
@@ -1227,6 +1266,13 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor frame_len, Tensor count, int ncap, Tensor(b!) ws, "
         "Tensor(c!) seqno) -> ()", &tree_seq_order);
   m.def("tree_digest(Tensor[] tree, Tensor(a!) out) -> ()", &tree_digest);
+  m.def("tree_list_workspace(int n) -> int", &tree_list_workspace);
+  m.def("tree_list(Tensor(a!)[] tree, Tensor rx, Tensor frame_off, "
+        "Tensor frame_len, Tensor count, int ncap, int wslot, int max_frame, "
+        "Tensor(b!) want, Tensor(c!) ws, Tensor(d!) out, int out_cap, "
+        "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
+        "bool terminate=False) -> ()",
+        &tree_list);
   m.def("watch_events(Tensor r_op, Tensor r_err, Tensor count, int ncap, "
         "Tensor fired, Tensor(a!) bsum, Tensor(b!) ev_slot, "
         "Tensor(c!) ev_type, Tensor(d!) ev_path_off, Tensor(e!) ev_path_len, "

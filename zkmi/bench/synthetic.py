@@ -371,6 +371,28 @@ class GpuTree(object):
                 return v
         return -1
 
+    def children_host(self, path):
+        """Sorted child names of ``path`` from the node table read back to
+        the host (``node_parent``, ``node_pw`` and the path arena; tests and
+        debugging), or None when no live node has that path.  The same join
+        the device list path does (:meth:`GpuServer.serve_list`)."""
+        n = min(int(self.counters[_lib.TC_NODES].item()), self.cap)
+        par = self.node_parent[:n].cpu().numpy()
+        pw = self.node_pw[:n].cpu().numpy()
+        arena = self.path_arena.cpu().numpy().tobytes()
+        off, ln = pw >> 24, pw & 0xFFFFFF
+        want = path.encode()
+        node = -1
+        for v in np.nonzero((par != NODE_FREE) & (ln == len(want)))[0]:
+            if arena[off[v]:off[v] + ln[v]] == want:
+                node = int(v)
+                break
+        if node < 0:
+            return None
+        skip = len(want) + 1
+        return sorted(arena[off[v] + skip:off[v] + ln[v]].decode()
+                      for v in np.nonzero(par == node)[0])
+
     def node_slot_host(self, v):
         """(data bytes, Stat) of node ``v`` read back from HBM (tests)."""
         from .. import jute
@@ -590,6 +612,56 @@ class GpuServer(object):
                 if wslot < 0:
                     raise ValueError('resume needs the watcher slot')
                 self._resume(rx, ft, wslot)
+
+    def serve_list(self, rx, n, wslot=-1, terminate=False, max_frame=None,
+                   out=None):
+        """Serve a batch of list requests — GET_CHILDREN / GET_CHILDREN2
+        frames only, ``rx[:n]`` (``n`` a host length or a device total) —
+        from the tree (csrc/kernels/tree.hip list_*: two sweeps of the node
+        table per batch, no child links).  Returns ``(out, total, err,
+        frame_table)`` like :meth:`serve`; the replies are in request order.
+
+        Any other op in the batch is answered UNIMPLEMENTED, a truncated
+        frame BAD_ARGUMENTS, a missing path NO_NODE — ``/`` included, which
+        has no node in this tree (every op on it is NO_NODE).  The order of
+        the names inside a reply is unspecified, as ZooKeeper's is.  A
+        request with ``watch`` set that finds its node arms the child watch
+        of watcher slot ``wslot`` (0..63; needs a tree with a watch table);
+        a NO_NODE arms nothing.  A reply frame longer than ``max_frame``
+        bytes (default: K1's 16 MiB cap) is answered SYSTEMERROR.  ``err``
+        2 with ``total`` 0: the replies did not fit ``out`` (default: the
+        server's reply buffer) and nothing was written.  Mixed batches go
+        through :meth:`serve`, which answers these two ops UNIMPLEMENTED.
+
+        A sharded tree (``shard`` with world > 1) raises: its parents count
+        children it does not index."""
+        tree = self.tree
+        if tree.shard is not None and tree.shard[1] > 1:
+            raise ValueError('serve_list: a sharded tree does not index '
+                             'every child of its parents')
+        dev = tree.device
+        if getattr(self, 'list_want', None) is None:
+            self.list_want = torch.full((tree.cap,), _lib.LIST_IDLE,
+                                        dtype=I32, device=dev)
+            self.list_ws = torch.empty(
+                _lib.tree_list_workspace(self.cap_frames), dtype=U8,
+                device=dev)
+            self.list_rec_off = torch.empty(self.cap_frames, dtype=I64,
+                                            device=dev)
+            self.list_total_err = B._total_err(dev)
+        if out is None:
+            out = self.out
+        if max_frame is None:
+            max_frame = consts.MAX_PACKET
+        ft = self.scanner.scan(rx, n)
+        total, err = self.list_total_err
+        _lib.tree_list(tree.tensors, rx, ft.off, ft.length, ft.count,
+                       self.cap_frames, wslot, max_frame, self.list_want,
+                       self.list_ws, out, out.numel(), self.list_rec_off,
+                       total, err, terminate)
+        self.last_rec_off = self.list_rec_off
+        self.result = (out, total, err, ft)
+        return self.result
 
     def _seq_order(self, rx, ft):
         """Number the batch's SEQUENTIAL creates in stream order (parent's
@@ -818,6 +890,122 @@ class GetPipeline(object):
         if self.gstate is not None and not validate:
             self.gstate[1:].add_(1)
         self.last = (self.idx, rep, rx, ft)
+
+
+class ListPipeline(object):
+    """Batched list() over the synthetic tree's directories: a fixed
+    K10-encoded batch of ``batch`` GET_CHILDREN2 requests, request ``k`` on
+    directory ``k % ndirs`` (``ndirs`` below the batch size: several
+    requests per directory, the duplicate path of the list kernels).
+
+    A step is :meth:`GpuServer.serve_list` on the request stream, then the
+    client half on the replies: K1, K2-K8 decode, and the children vectors
+    expanded to one (offset, length) row per name.  The device check adds to
+    ``bad`` every reply that is not a clean OK, whose child count differs
+    from its Stat's numChildren, and a step whose string bytes differ from
+    the tree's (counted on the host when the pipeline is built); a good
+    step adds ``batch`` to ``acc``.  No host read inside a step."""
+
+    def __init__(self, tree, batch, ndirs=None):
+        self.tree = tree
+        self.batch = n = batch
+        self.dev = dev = tree.device
+        L = _lib.lib()
+        all_dirs = tree.leaf0 - 1
+        ndirs = all_dirs if ndirs is None else min(int(ndirs), all_dirs)
+        self.ndirs = ndirs
+        didx = 1 + (np.arange(n, dtype=np.int64) % ndirs)
+        # each directory's children and name bytes, from the node table
+        nn = min(int(tree.counters[_lib.TC_NODES].item()), tree.cap)
+        par = tree.node_parent[:nn].cpu().numpy()
+        ln = (tree.node_pw[:nn].cpu().numpy() & 0xFFFFFF)
+        kid = par >= 0
+        cnt = np.bincount(par[kid], minlength=nn)
+        nbytes = np.bincount(par[kid], weights=(ln[kid] - ln[par[kid]] + 3),
+                             minlength=nn).astype(np.int64)
+        self.want_children = int(cnt[didx].sum())
+        self.want_bytes = int(nbytes[didx].sum())
+        frame = 4 + 16 + 4 + nbytes[didx] + 68
+        out_cap = int(frame.sum()) + 64
+        idx = torch.from_numpy(didx).to(dev)
+        self.xt = B.XidTable(bits=max(20, (n - 1).bit_length() + 1),
+                             device=dev)
+        z64 = torch.zeros(n, dtype=I64, device=dev)
+        z32 = torch.zeros(n, dtype=I32, device=dev)
+        rb = B.RequestBatch(
+            n, torch.full((n,), consts.OP_CODES['GET_CHILDREN2'], dtype=I32,
+                          device=dev),
+            torch.arange(n, dtype=I32, device=dev), z32,
+            tree.node_path_off[idx].contiguous(),
+            tree.node_path_len[idx].contiguous(), z64, z32, z32,
+            tree.path_arena, tree.slab, torch.zeros(1, dtype=I64, device=dev),
+            torch.zeros(1, dtype=I32, device=dev),
+            torch.zeros(16, dtype=U8, device=dev))
+        maxpath = int(tree.node_path_len[idx].max().item())
+        tx = torch.empty(n * (17 + maxpath) + 64, dtype=U8, device=dev)
+        self.tx, _, self.tx_total, _ = B.encode_requests(rb, self.xt, out=tx)
+        self.server = GpuServer(tree, n, out_cap,
+                                window=B.frame_window(17 + maxpath),
+                                seq_order=False)
+        self.rscanner = B.FrameScanner(
+            n, dev, window=B.frame_window(int(frame.max())))
+        self.reply = B.alloc_replies(n, dev)
+        self.reply.aux0.zero_()
+        # one row per child name; the names sit in the reply buffer, 4 bytes
+        # of length each at least, so this bounds them whatever the replies
+        self.str_cap = out_cap // 4 + 1
+        self.soff = torch.empty(self.str_cap, dtype=I64, device=dev)
+        self.slen = torch.empty(self.str_cap, dtype=I32, device=dev)
+        self.row_base = torch.empty(n, dtype=I64, device=dev)
+        self.nstr = torch.zeros(1, dtype=I64, device=dev)
+        self.scan_ws = torch.empty(L.scan_workspace(n), dtype=I64, device=dev)
+        self.bad = torch.zeros(1, dtype=I64, device=dev)
+        self.last = None
+
+    def capture(self, acc):
+        """One step as a HIP graph (run an eager step first)."""
+        return _capture_steps(self, acc)
+
+    def server_step(self):
+        """The server half alone: K1 on the requests and the list kernels."""
+        return self.server.serve_list(self.tx, self.tx_total)
+
+    def step(self, validate=True, acc=None):
+        if validate and acc is None:
+            acc = torch.zeros(1, dtype=I64, device=self.dev)
+        L = _lib.lib()
+        n = self.batch
+        rx, rtotal, rerr, _ = self.server_step()
+        ft = self.rscanner.scan(rx, _len(rtotal))
+        rep = self.reply
+        # (rows past the frames K1 found keep a zero count: nothing of a
+        # short stream is expanded)
+        rep.aux0.zero_()
+        B.decode_replies(rx, ft, self.xt, out=rep)
+        L.scan_excl(rep.aux0, self.row_base, self.nstr, self.scan_ws)
+        L.expand_strings(rx, rep.pay_off, rep.aux0, self.row_base, self.soff,
+                         self.slen)
+        self.last = (rep, rx, ft, rtotal)
+        if not validate:
+            return None
+        bad = ((rep.err != 0) | (rep.status != 0) |
+               (rep.aux0 != rep.stat32[4])).sum()
+        bad = bad + (ft.count[0] != n).to(I64) + (rerr[0] != 0).to(I64)
+        bad = bad + (rep.pay_len.sum() != self.want_bytes).to(I64)
+        bad = bad + (self.nstr[0] != self.want_children).to(I64)
+        self.bad.add_(bad)
+        acc.add_(n * (bad == 0).to(I64))
+        return acc
+
+    def diagnose(self):
+        """Host view of the last step's replies (after a failed check)."""
+        rep, rx, ft, rtotal = self.last
+        return {'frames': ft.host_result(), 'total': int(rtotal.item()),
+                'err': rep.err.unique().cpu().tolist(),
+                'children': int(rep.aux0.sum().item()),
+                'want_children': self.want_children,
+                'string_bytes': int(rep.pay_len.sum().item()),
+                'want_bytes': self.want_bytes, 'bad': int(self.bad.item())}
 
 
 def _arena(strings, dev):

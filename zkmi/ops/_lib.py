@@ -93,5 +93,28 @@ def set_scan_mode(mode):
     return lib().scan_set_mode(mode)
 
 
+# idle value of the list path's per-node claim words (tree.hip LS_NONE)
+LIST_IDLE = 0x7fffffff
+
+
+def tree_list_workspace(ncap):
+    """Bytes of the workspace :func:`tree_list` needs for ``ncap`` requests
+    (a uint8 tensor; nothing in it needs zeroing)."""
+    return lib().tree_list_workspace(int(ncap))
+
+
+def tree_list(tree, rx, frame_off, frame_len, count, ncap, wslot, max_frame,
+              want, ws, out, out_cap, rec_off, total, err, terminate=False):
+    """Serve a batch of GET_CHILDREN / GET_CHILDREN2 frames from the HBM
+    tree (csrc/kernels/tree.hip list_*), on the current stream: the framed
+    replies in request order -> ``out[:total]``, their starts ->
+    ``rec_off``.  ``want``: int32 per node slot, all :data:`LIST_IDLE`
+    between calls (the kernels put it back).  ``err`` 2 and ``total`` 0:
+    the stream did not fit ``out_cap``."""
+    lib().tree_list(tree, rx, frame_off, frame_len, count, int(ncap),
+                    int(wslot), int(max_frame), want, ws, out, int(out_cap),
+                    rec_off, total, err, bool(terminate))
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
