@@ -411,15 +411,15 @@ int zk_decode_replies(const uint8_t* buf, const int64_t* foff,
 // acc `slots` (1..64) int64 counters the caller sums; slab / slot_off
 // (optional, both or neither): the tree's node slots, for the sampled
 // payload comparison.
-int zk_decode_replies_check2(const uint8_t* buf, const int64_t* foff,
-                             const int32_t* flen, const int64_t* n_dev,
-                             int64_t ncap, const int64_t* xid_tab,
-                             int64_t xid_mask, const ZkReplyOut* o,
-                             const int64_t* idx, const int32_t* xid,
-                             const int32_t* data_len, unsigned long long* acc,
-                             int32_t slots, int64_t* tick,
-                             const uint8_t* slab, const int64_t* slot_off,
-                             hipStream_t st) {
+int zk_decode_replies_check(const uint8_t* buf, const int64_t* foff,
+                            const int32_t* flen, const int64_t* n_dev,
+                            int64_t ncap, const int64_t* xid_tab,
+                            int64_t xid_mask, const ZkReplyOut* o,
+                            const int64_t* idx, const int32_t* xid,
+                            const int32_t* data_len, unsigned long long* acc,
+                            int32_t slots, int64_t* tick,
+                            const uint8_t* slab, const int64_t* slot_off,
+                            hipStream_t st) {
   if (ncap <= 0) return 0;
   if (slots < 1 || slots > 64) return (int)hipErrorInvalidValue;
   if ((slab == nullptr) != (slot_off == nullptr))

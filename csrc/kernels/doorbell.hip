@@ -251,7 +251,7 @@ void* zk_db_create(int32_t nslots) {
   return d;
 }
 
-// Launch the resident wave; it serves tickets from d->next on and leaves
+// Launch the resident wave; it serves ticket d->next and on, and leaves
 // after max_ms at the latest.
 int zk_db_start(void* h, int64_t max_ms) {
   ZkDb* d = (ZkDb*)h;

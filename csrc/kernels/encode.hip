@@ -46,12 +46,10 @@ ZK_DEV int64_t req_body_size(const ZkReqBatch& b, int64_t i, bool* ok) {
   }
 }
 
-// Offsets are reduce-then-scan fused into the producer and the consumer:
-// the sizes kernel also writes its block's sum and the write kernel sums
-// the block sums before its own (sum_blocks) and adds a block scan of the
-// sizes.  Two launches where a separate device-wide scan made five (and a
-// one-workgroup scan of the block sums between them made three, until
-// round 5; it is still used past FUSED_SCAN_BLOCKS).
+// Offsets are reduce-then-scan: the sizes kernel also writes its block's
+// sum, a one-workgroup scan of the block sums gives every block its base
+// (zk_scan_small_i64 -> bbase) and the write kernel adds a block scan of the
+// sizes.  Three launches where a separate device-wide scan made five.
 // A malformed request is flagged per block (bbad, a plain store every
 // launch) and req_write's block 0 folds the flags into err, so err needs no
 // zeroing launch before the encode.
@@ -176,25 +174,17 @@ __global__ __launch_bounds__(ENC_T) void resp_sizes(ZkRespBatch r,
 // dword can be shared with a neighbour, and those are OR-ed into the
 // zero-initialised image (ds_or_b32), everything else is a plain ds_write.
 //
-// The image is bank-swizzled: dword w lives at swz(w) = w ^ ((w >> 4) & 31),
-// a permutation inside each aligned 32-dword group.  Lanes emit their
-// records in lockstep, so their k-th dwords sit one record apart; ds_write_b32
-// banks are (dword mod 32) over 32-lane groups, and at 192-byte records (48
-// dwords) an unswizzled image put 16 lanes on a bank.  Any swizzle that
-// keeps aligned 4-dword groups together (rounds 1-4: bits 2-5 XORed with the
-// 64-dword row, 2.49 M conflict cycles a 512K-reply dispatch) leaves lanes
-// writing dword k of 4-aligned records on 8 banks, 4-way; this one moves
-// bits 0-1 too (conflict-free at 48 dwords; 2-3 way for odd record sizes),
-// so the read-out assembles each 16-byte vector from four dword reads
-// (~2.4-way on those reads, against 4-way on every record write before).
-// SW = 1: the rounds 1-4 swizzle (bits 2-5 XOR the 64-dword row: 4-dword
-// groups stay whole, the read-out moves 16-byte vectors; 4-way on the
-// record writes), kept for A/B (ZKMI_ENC_SWZ=1).
-template <int SW>
-ZK_DEV int64_t swz(int64_t w) {
-  if (SW == 1) return w ^ (((w >> 6) & 15) << 2);
-  return w ^ ((w >> 4) & 31);
-}
+// The image is bank-swizzled: dword w lives at swz(w), bits 2-5 XORed with
+// the 64-dword row.  Lanes emit their records in lockstep, so their k-th
+// dwords sit one record apart; ds_write_b32 banks are (dword mod 32) over
+// 32-lane groups, and at 192-byte records (48 dwords) an unswizzled image
+// put 16 lanes on a bank.  This swizzle keeps aligned 4-dword groups whole:
+// 4-way conflicts on the record writes, but the read-out moves 16-byte
+// vectors.  One that moves bits 0-1 too (w ^ ((w >> 4) & 31)) is
+// conflict-free on the writes and assembles each vector from four dword
+// reads; it cost the GET step 0.5 %: the dword reads took more LDS issue
+// than the conflicts did (profiles/r5_encoder_ab.md).
+ZK_DEV int64_t swz(int64_t w) { return w ^ (((w >> 6) & 15) << 2); }
 struct GSink {
   uint8_t* o;
   ZK_DEV void be32(int32_t v) { st_be32(o, v); o += 4; }
@@ -205,7 +195,6 @@ struct GSink {
   ZK_DEV void finish() {}
 };
 
-template <int SW>
 struct LSink {
   uint32_t* w;
   int64_t widx;
@@ -216,8 +205,8 @@ struct LSink {
                                              nb((int)(rel & 3)), first(true) {}
   ZK_DEV void flush() {
     const uint32_t v = (uint32_t)acc;
-    if (first) { atomicOr(&w[swz<SW>(widx)], v); first = false; }
-    else w[swz<SW>(widx)] = v;
+    if (first) { atomicOr(&w[swz(widx)], v); first = false; }
+    else w[swz(widx)] = v;
     ++widx;
     acc >>= 32;
     nb -= 4;
@@ -261,7 +250,7 @@ struct LSink {
     for (; i < n; ++i) u8(s[i]);
   }
   ZK_DEV void finish() {
-    if (nb > 0) atomicOr(&w[swz<SW>(widx)], (uint32_t)acc);
+    if (nb > 0) atomicOr(&w[swz(widx)], (uint32_t)acc);
   }
 };
 
@@ -403,71 +392,20 @@ ZK_DEV void block_offsets(int64_t r0, int64_t r1,
   __syncthreads();
 }
 
-// The write pass's block base without a scan launch: the sizes pass wrote
-// every block's sum (bsum, complete: an earlier launch), so block b sums
-// bsum[0, b) itself — four independent L2 loads a thread per 1024 blocks,
-// one round trip at the usual batch sizes.  Past FUSED_SCAN_BLOCKS the sum
-// grows with the grid (quadratic traffic) and the host scans bsum first
-// (zk_scan_small_i64 -> bbase).  Also the grand total, for the block that
-// needs it (the last one: it writes *total, err and the terminator).
-constexpr int64_t FUSED_SCAN_BLOCKS = 4096;
-
-ZK_DEV int64_t sum_blocks(const int64_t* __restrict__ bsum, int64_t b,
-                          int64_t* sm) {
-  int64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  int64_t k = threadIdx.x;
-  for (; k + 3 * ENC_T < b; k += 4 * ENC_T) {
-    a0 += bsum[k];
-    a1 += bsum[k + ENC_T];
-    a2 += bsum[k + 2 * ENC_T];
-    a3 += bsum[k + 3 * ENC_T];
-  }
-  for (; k < b; k += ENC_T) a0 += bsum[k];
-  int64_t tot;
-  block_excl_scan(a0 + a1 + a2 + a3, sm, &tot);
-  return tot;
-}
-
-// This block's base (bbase, or fused: sum_blocks) and, in the last block,
-// the stream total (fused: computed and stored; else read).
-ZK_DEV int64_t block_base(const int64_t* __restrict__ bbase,
-                          const int64_t* __restrict__ bsum,
-                          int64_t* __restrict__ total, int64_t* sm,
-                          int64_t* T) {
-  const int64_t b = blockIdx.x;
-  if (bsum == nullptr) {
-    *T = *total;
-    return bbase[b];
-  }
-  const int64_t base = sum_blocks(bsum, b, sm);
-  *T = -1;                              // (known in the last block only)
-  if (b == (int64_t)gridDim.x - 1) {
-    *T = base + bsum[b];
-    if (threadIdx.x == 0) *total = *T;
-  }
-  return base;
-}
-
-template <int SW>
 ZK_DEV uint8_t lds_byte(const uint32_t* lw, int64_t b) {
-  return ((const uint8_t*)(lw + swz<SW>(b >> 2)))[b & 3];
+  return ((const uint8_t*)(lw + swz(b >> 2)))[b & 3];
 }
 
-// 16 image bytes at image byte y (16-aligned): four dword reads (the
-// swizzle scatters a 4-dword group over banks), one 16-byte vector.
-template <int SW>
+// 16 image bytes at image byte y (16-aligned): the swizzle keeps a 4-dword
+// group whole, so one 16-byte read.
 ZK_DEV uint4 lds_vec(const uint32_t* lw, int64_t y) {
-  const int64_t w = y >> 2;
-  if (SW == 1) return *(const uint4*)(lw + swz<SW>(w));
-  return make_uint4(lw[swz<SW>(w)], lw[swz<SW>(w + 1)], lw[swz<SW>(w + 2)],
-                    lw[swz<SW>(w + 3)]);
+  return *(const uint4*)(lw + swz(y >> 2));
 }
 
 // Stream the block's LDS image [B0, B1) (image base a0 = B0 & ~15) out to
 // global memory: the 16-byte aligned interior with dwordx4 stores (a dword
 // a lane — four times the store instructions — cost the GET step 4 %), the
 // <= 15 head / tail bytes with byte stores (they abut other blocks' spans).
-template <int SW>
 ZK_DEV void stage_out(const uint32_t* lw, int64_t a0, int64_t B0, int64_t B1,
                       uint8_t* __restrict__ out) {
   const int64_t c0 = (B0 + 15) & ~(int64_t)15;
@@ -475,18 +413,18 @@ ZK_DEV void stage_out(const uint32_t* lw, int64_t a0, int64_t B0, int64_t B1,
   if (c0 < c1) {
     for (int64_t x = c0 + (int64_t)threadIdx.x * 16; x < c1;
          x += (int64_t)blockDim.x * 16)
-      *(uint4*)(out + x) = lds_vec<SW>(lw, x - a0);
+      *(uint4*)(out + x) = lds_vec(lw, x - a0);
     const int64_t hb = c0 - B0, tb = B1 - c1;
     if ((int64_t)threadIdx.x < hb) {
       const int64_t x = B0 + threadIdx.x;
-      out[x] = lds_byte<SW>(lw, x - a0);
+      out[x] = lds_byte(lw, x - a0);
     } else if ((int64_t)threadIdx.x >= 16 && (int64_t)threadIdx.x < 16 + tb) {
       const int64_t x = c1 + threadIdx.x - 16;
-      out[x] = lds_byte<SW>(lw, x - a0);
+      out[x] = lds_byte(lw, x - a0);
     }
   } else {
     for (int64_t x = B0 + threadIdx.x; x < B1; x += blockDim.x)
-      out[x] = lds_byte<SW>(lw, x - a0);
+      out[x] = lds_byte(lw, x - a0);
   }
 }
 
@@ -496,17 +434,17 @@ ZK_DEV void stage_out(const uint32_t* lw, int64_t a0, int64_t B0, int64_t B1,
 // run, counted with one barrier); a single record larger than the image is
 // written straight to global memory.  off / sizes are the block's EncLocal
 // tables (index i - r0).
-template <int SW, class F>
+template <class F>
 ZK_DEV void staged_emit(int64_t r0, int64_t r1, const int64_t* off,
                         const int64_t* sizes, uint8_t* __restrict__ out,
-                        uint32_t* lw, F emit, int64_t stage = STAGE_BYTES) {
+                        uint32_t* lw, F emit) {
   int64_t rs = r0;
   while (rs < r1) {                              // block-uniform
     const int64_t B0 = off[rs - r0];
     const int64_t a0 = B0 & ~(int64_t)15;
     const int64_t i = rs + threadIdx.x;
     const bool fits = i < r1 &&
-                      off[i - r0] + sizes[i - r0] - a0 + 16 <= stage;
+                      off[i - r0] + sizes[i - r0] - a0 + 16 <= STAGE_BYTES;
     const int k = __syncthreads_count(fits);
     if (k == 0) {
       if (threadIdx.x == 0) {
@@ -523,11 +461,11 @@ ZK_DEV void staged_emit(int64_t r0, int64_t r1, const int64_t* off,
       ((uint4*)lw)[x] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     if (i < re) {
-      LSink<SW> l(lw, off[i - r0] - a0);
+      LSink l(lw, off[i - r0] - a0);
       emit(l, i);
     }
     __syncthreads();
-    stage_out<SW>(lw, a0, B0, B1, out);
+    stage_out(lw, a0, B0, B1, out);
     __syncthreads();                             // image reused next run
     rs = re;
   }
@@ -571,7 +509,6 @@ ZK_DEV int64_t hole_h0(int64_t off) { return (off + 20 + 15) & ~(int64_t)15; }
 // in the block's list); image position y of segment k is out position
 // y + a0c + (hole bytes before it).  One thread per segment; the run's first
 // and last 16-byte chunks are shared with other runs / blocks (byte stores).
-template <int SW>
 ZK_DEV void stage_out_segs(const uint32_t* lw, int64_t a0c, int64_t B0,
                            int64_t B1, int64_t yend, int64_t hb0, int64_t K,
                            int64_t j0, const int64_t* off, const EncHoles& H,
@@ -595,7 +532,7 @@ ZK_DEV void stage_out_segs(const uint32_t* lw, int64_t a0c, int64_t B0,
     }
     for (int64_t y = y0 & ~(int64_t)15; y < y1; y += 16) {
       const int64_t x = y + a0c + d;
-      const uint4 v = lds_vec<SW>(lw, y);
+      const uint4 v = lds_vec(lw, y);
       if (x >= B0 && x + 16 <= B1) {
         *(uint4*)(out + x) = v;
       } else {
@@ -647,11 +584,11 @@ ZK_DEV void copy_hole_q(const uint8_t* __restrict__ src, uint8_t* dst,
 
 // staged_emit for replies with holes.  off / sizes: the block's EncLocal
 // tables; H: the holes (set up by resp_write).
-template <int SW, class F>
+template <class F>
 ZK_DEV void staged_emit_holes(int64_t r0, int64_t r1, const int64_t* off,
                               const int64_t* sizes, EncHoles& H,
-                              uint8_t* __restrict__ out, uint32_t* lw, F emit,
-                              int64_t stage) {
+                              uint8_t* __restrict__ out, uint32_t* lw,
+                              F emit) {
   int64_t rs = r0;
   while (rs < r1) {                              // block-uniform
     const int64_t ls = rs - r0;
@@ -661,7 +598,7 @@ ZK_DEV void staged_emit_holes(int64_t r0, int64_t r1, const int64_t* off,
     const int64_t i = rs + threadIdx.x;
     const int64_t li = i - r0;
     const bool fits = i < r1 && off[li] - (H.hb[li] >> 9) + sizes[li] -
-                                        H.hole[li] - a0c + 16 <= stage;
+                                        H.hole[li] - a0c + 16 <= STAGE_BYTES;
     const int k = __syncthreads_count(fits);
     if (k == 0) {
       // one record larger than the image, compacted: written whole
@@ -683,7 +620,7 @@ ZK_DEV void staged_emit_holes(int64_t r0, int64_t r1, const int64_t* off,
       ((uint4*)lw)[x] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     if (i < re) {
-      LSink<SW> l(lw, off[li] - (H.hb[li] >> 9) - a0c);
+      LSink l(lw, off[li] - (H.hb[li] >> 9) - a0c);
       const int64_t hl = H.hole[li];
       emit(l, i, hl ? hole_h0(off[li]) - (off[li] + 20) : 0, hl);
     }
@@ -691,9 +628,9 @@ ZK_DEV void staged_emit_holes(int64_t r0, int64_t r1, const int64_t* off,
     const int64_t j0 = H.hb[ls] & 511;
     const int64_t K = ((H.hb[le] & 511) + (H.hole[le] ? 1 : 0)) - j0;
     if (K == 0) {
-      stage_out<SW>(lw, B0 & ~(int64_t)15, B0, B1, out);
+      stage_out(lw, B0 & ~(int64_t)15, B0, B1, out);
     } else {
-      stage_out_segs<SW>(lw, a0c, B0, B1, yend, hb0, K, j0, off, H, out);
+      stage_out_segs(lw, a0c, B0, B1, yend, hb0, K, j0, off, H, out);
     }
     __syncthreads();                             // image reused next run
     rs = re;
@@ -766,25 +703,21 @@ ZK_DEV void emit_uniform(const ZkRespBatch& r, const ZkNodeStore& s,
   }
 }
 
-// bsum != null: fused (block_base); every block checks its own span
-// against cap, the last one writes *total and err (2: over capacity, the
-// stream is then incomplete).
-template <int SW>
+// bbase: every block's base; *total: the stream's bytes.  Block 0 writes
+// err (2: over capacity, nothing is then written) and the terminator.
 __global__ __launch_bounds__(ENC_T) void resp_write(
     ZkRespBatch r, ZkNodeStore s, const int64_t* __restrict__ n_dev,
     int64_t ncap, const int64_t* __restrict__ sizes,
-    const int64_t* __restrict__ bbase, const int64_t* __restrict__ bsum,
-    int64_t* __restrict__ rec_off, int64_t* __restrict__ total,
-    uint8_t* __restrict__ out, int64_t cap, int32_t* __restrict__ err,
-    int32_t term, int64_t stage, int32_t uniform) {
+    const int64_t* __restrict__ bbase, int64_t* __restrict__ rec_off,
+    const int64_t* __restrict__ total, uint8_t* __restrict__ out, int64_t cap,
+    int32_t* __restrict__ err, int32_t term, int32_t uniform) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lw[];
   __shared__ EncLocal E;
   const int64_t n = min(*n_dev, ncap);
   const int64_t r0 = (int64_t)blockIdx.x * ENC_T;
-  int64_t T;
-  const int64_t base = block_base(bbase, bsum, total, E.sm, &T);
-  const bool last = blockIdx.x == gridDim.x - 1;
-  if (bsum != nullptr ? last : blockIdx.x == 0) {
+  const int64_t T = *total;
+  const int64_t base = bbase[blockIdx.x];
+  if (blockIdx.x == 0) {
     put_terminator(term, T, out, cap);
     // err written whole by one thread (no zeroing launch before the encode)
     if (threadIdx.x == 0) *err = T > cap ? 2 : 0;
@@ -792,7 +725,6 @@ __global__ __launch_bounds__(ENC_T) void resp_write(
   if (r0 >= n) return;
   if (T > cap) return;
   const int64_t r1 = min(r0 + ENC_T, n);
-  if (bsum != nullptr && base + bsum[blockIdx.x] > cap) return;
   block_offsets(r0, r1, sizes, base, rec_off, E);
   // uniform GET_DATA replies: straight from the slots (emit_uniform)
   if (uniform) {                                  // (a kernel argument)
@@ -802,7 +734,7 @@ __global__ __launch_bounds__(ENC_T) void resp_write(
                    (r.opcode[i] == OP_GET_DATA && r.err[i] == ERR_OK &&
                     E.sz[threadIdx.x] == S);
     if (__syncthreads_and(u) && (S & 15) == 0 && (E.off[0] & 15) == 0 &&
-        S >= 96 && stage >= 5 * 4 * ENC_T + 8 * ENC_T) {
+        S >= 96) {
       emit_uniform(r, s, r0, r1 - r0, S, E.off[0], out, lw);
       return;
     }
@@ -827,10 +759,10 @@ __global__ __launch_bounds__(ENC_T) void resp_write(
     if (hole) H.bl[hb & 511] = (int16_t)threadIdx.x;
     __syncthreads();
   }
-  staged_emit_holes<SW>(r0, r1, E.off, E.sz, H, out, lw,
+  staged_emit_holes(r0, r1, E.off, E.sz, H, out, lw,
                     [&](auto& k, int64_t i, int64_t pre, int64_t hole) {
     emit_response(k, r, s, i, E.sz[i - r0] - 4, pre, hole);
-  }, stage);
+  });
   __syncthreads();                 // (bl: records written whole)
   // the holes: four replies per wave-iteration, one per 16-lane quarter,
   // each quarter's loads all issued before its stores
@@ -932,20 +864,19 @@ ZK_DEV void emit_request(K& k, const ZkReqBatch& b, int64_t i, int64_t body) {
 // the frame bytes as partial-line writes: WRITE_SIZE 254 MB for a 36 MB
 // GET_DATA stream).  Unknown opcodes were flagged by req_sizes and get
 // size 0 (nothing written).
-template <int SW>
 __global__ __launch_bounds__(ENC_T) void req_write(
     ZkReqBatch b, int64_t n, const int64_t* __restrict__ sizes,
-    const int64_t* __restrict__ bbase, const int64_t* __restrict__ bsum,
-    int64_t* __restrict__ rec_off, int64_t* __restrict__ total,
-    uint8_t* __restrict__ out, int64_t cap, int64_t* __restrict__ xid_tab,
-    int64_t xid_mask, int32_t* __restrict__ err, int32_t term,
+    const int64_t* __restrict__ bbase, int64_t* __restrict__ rec_off,
+    const int64_t* __restrict__ total, uint8_t* __restrict__ out, int64_t cap,
+    int64_t* __restrict__ xid_tab, int64_t xid_mask,
+    int32_t* __restrict__ err, int32_t term,
     const int64_t* __restrict__ bbad, int64_t nb) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lw[];
   __shared__ EncLocal E;
   const int64_t r0 = (int64_t)blockIdx.x * ENC_T;
-  int64_t T;
-  const int64_t base = block_base(bbase, bsum, total, E.sm, &T);
-  if (bsum != nullptr ? blockIdx.x == gridDim.x - 1 : blockIdx.x == 0) {
+  const int64_t T = *total;
+  const int64_t base = bbase[blockIdx.x];
+  if (blockIdx.x == 0) {
     put_terminator(term, T, out, cap);
     // err, written whole (1: a malformed request, 2: over capacity)
     int64_t e = 0;
@@ -956,10 +887,8 @@ __global__ __launch_bounds__(ENC_T) void req_write(
   if (r0 >= n) return;
   if (T > cap) return;                      // capacity guard (whole batch)
   const int64_t r1 = min(r0 + ENC_T, n);
-  // fused: each block's own span (the last block flags the batch)
-  if (bsum != nullptr && base + bsum[blockIdx.x] > cap) return;
   block_offsets(r0, r1, sizes, base, rec_off, E);
-  staged_emit<SW>(r0, r1, E.off, E.sz, out, lw, [&](auto& k, int64_t i) {
+  staged_emit(r0, r1, E.off, E.sz, out, lw, [&](auto& k, int64_t i) {
     const int64_t sz = E.sz[i - r0];
     if (sz > 0) emit_request(k, b, i, sz - 4);
   });
@@ -1002,20 +931,6 @@ static inline unsigned nblk(int64_t n) {
   return (unsigned)((n + ENC_T - 1) / ENC_T);
 }
 
-// A/B switches, read once (profiles/r5_encoder_ab.md, GET step, 2 x 50
-// steps each): the image swizzle — 1 (default) keeps 4-dword groups whole
-// (4-way conflicts on the record writes, 16-byte read-out), 0 scatters
-// them (conflict-free writes, four dword reads per 16-byte vector): 0
-// removes the conflict cycles and costs the step 0.5 %, the dword reads
-// cost more LDS issue than the conflicts did; the block sums — a one-
-// workgroup scan launch (default) or every write block summing the sums
-// before its own (ZKMI_ENC_FUSED=1: one launch less, but 1.3 % slower: each
-// block's sum is a round trip before its first store).
-static int enc_swz() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ZKMI_ENC_SWZ"); v = e ? atoi(e) : 1; }
-  return v;
-}
 // Uniform GET_DATA reply blocks written straight from the slots
 // (emit_uniform; ZKMI_ENC_UNIFORM=0 sends them through the LDS image).
 // Its first version ran the GET step at 0.958 ms against the image's 0.651
@@ -1026,22 +941,17 @@ static int enc_uniform() {
   if (v < 0) { const char* e = getenv("ZKMI_ENC_UNIFORM"); v = e ? atoi(e) : 1; }
   return v;
 }
-static bool enc_fused() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ZKMI_ENC_FUSED"); v = e ? atoi(e) : 0; }
-  return v != 0;
-}
 
 }  // namespace zk
 
 extern "C" {
 
 // terminate != 0: four 0xFF bytes follow the stream (put_terminator).
-int zk_encode_requests2(const ZkReqBatch* b, int64_t n, int64_t* sizes,
-                        int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                        uint8_t* out, int64_t out_cap, int64_t* xid_tab,
-                        int64_t xid_mask, int32_t* err, int32_t terminate,
-                        hipStream_t st) {
+int zk_encode_requests(const ZkReqBatch* b, int64_t n, int64_t* sizes,
+                       int64_t* rec_off, int64_t* total, int64_t* scan_ws,
+                       uint8_t* out, int64_t out_cap, int64_t* xid_tab,
+                       int64_t xid_mask, int32_t* err, int32_t terminate,
+                       hipStream_t st) {
   if (n <= 0) {
     int rc = hipMemsetAsync(total, 0, 8, st);
     if (!rc) rc = hipMemsetAsync(err, 0, 4, st);
@@ -1054,24 +964,16 @@ int zk_encode_requests2(const ZkReqBatch* b, int64_t n, int64_t* sizes,
   int64_t* bbad = scan_ws + 2 * nb;
   zk::req_sizes<<<nb, zk::ENC_T, 0, st>>>(*b, n, sizes, bbad, bsum);
   ZK_LAUNCH_CHECK();
-  const bool fused = nb <= zk::FUSED_SCAN_BLOCKS && zk::enc_fused();
-  if (!fused) {
-    int rc = zk_scan_small_i64(bsum, bbase, nb, total, st);
-    if (rc) return rc;
-  }
-  if (zk::enc_swz() == 1)
-    zk::req_write<1><<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
-        *b, n, sizes, bbase, fused ? bsum : nullptr, rec_off, total, out,
-        out_cap, xid_tab, xid_mask, err, terminate, bbad, (int64_t)nb);
-  else
-    zk::req_write<0><<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
-        *b, n, sizes, bbase, fused ? bsum : nullptr, rec_off, total, out,
-        out_cap, xid_tab, xid_mask, err, terminate, bbad, (int64_t)nb);
+  int rc = zk_scan_small_i64(bsum, bbase, nb, total, st);
+  if (rc) return rc;
+  zk::req_write<<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
+      *b, n, sizes, bbase, rec_off, total, out, out_cap, xid_tab, xid_mask,
+      err, terminate, bbad, (int64_t)nb);
   ZK_LAUNCH_CHECK();
   return 0;
 }
 
-// zk_encode_requests2 with the sizes pass done by the producer of the batch
+// zk_encode_requests with the sizes pass done by the producer of the batch
 // (bench_gen_get): `sizes` (frame bytes per request) and `bsum` (their sum
 // per 256-request block) are given, every request well-formed.  Two
 // launches: the block sums' scan, the write.
@@ -1083,31 +985,17 @@ int zk_encode_requests_presized(const ZkReqBatch* b, int64_t n,
                                 int64_t xid_mask, int32_t* err,
                                 int32_t terminate, hipStream_t st) {
   if (n <= 0)
-    return zk_encode_requests2(b, n, nullptr, rec_off, total, scan_ws, out,
-                               out_cap, xid_tab, xid_mask, err, terminate,
-                               st);
+    return zk_encode_requests(b, n, nullptr, rec_off, total, scan_ws, out,
+                              out_cap, xid_tab, xid_mask, err, terminate, st);
   const unsigned nb = zk::nblk(n);
   int64_t* bbase = scan_ws + nb;
   int rc = zk_scan_small_i64(bsum, bbase, nb, total, st);
   if (rc) return rc;
-  if (zk::enc_swz() == 1)
-    zk::req_write<1><<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
-        *b, n, sizes, bbase, nullptr, rec_off, total, out, out_cap, xid_tab,
-        xid_mask, err, terminate, nullptr, 0);
-  else
-    zk::req_write<0><<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
-        *b, n, sizes, bbase, nullptr, rec_off, total, out, out_cap, xid_tab,
-        xid_mask, err, terminate, nullptr, 0);
+  zk::req_write<<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
+      *b, n, sizes, bbase, rec_off, total, out, out_cap, xid_tab, xid_mask,
+      err, terminate, nullptr, 0);
   ZK_LAUNCH_CHECK();
   return 0;
-}
-
-int zk_encode_requests(const ZkReqBatch* b, int64_t n, int64_t* sizes,
-                       int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                       uint8_t* out, int64_t out_cap, int64_t* xid_tab,
-                       int64_t xid_mask, int32_t* err, hipStream_t st) {
-  return zk_encode_requests2(b, n, sizes, rec_off, total, scan_ws, out,
-                             out_cap, xid_tab, xid_mask, err, 0, st);
 }
 
 // Returns the frame length through *frame_len (device int64): 4 + body.
@@ -1151,33 +1039,11 @@ int zk_encode_connect_requests(const int32_t* proto, const int64_t* zxid,
 // presized != 0: `sizes` (frame size per reply, 0 past *n_dev) and the
 // per-256-reply block sums in scan_ws[0, nblk(ncap)) were already written
 // by the producer (zk_tree_serve), so the sizes pass is skipped.
-// stage (bytes, 0: STAGE_BYTES): the LDS each workgroup gets — the image of
-// its replies, or the uniform writer's header table (7 KiB).  A caller whose
-// replies are uniform GET_DATA blocks (the GET pipeline) asks for little, so
-// more workgroups (and another stream's kernels) fit a CU.
-int zk_encode_responses3(const ZkRespBatch* r, const ZkNodeStore* s,
-                         const int64_t* n_dev, int64_t ncap, int64_t* sizes,
-                         int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                         uint8_t* out, int64_t out_cap, int32_t* err,
-                         int32_t presized, int32_t terminate, int64_t stage,
-                         hipStream_t st);
-
-int zk_encode_responses2(const ZkRespBatch* r, const ZkNodeStore* s,
-                         const int64_t* n_dev, int64_t ncap, int64_t* sizes,
-                         int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                         uint8_t* out, int64_t out_cap, int32_t* err,
-                         int32_t presized, int32_t terminate, hipStream_t st) {
-  return zk_encode_responses3(r, s, n_dev, ncap, sizes, rec_off, total,
-                              scan_ws, out, out_cap, err, presized, terminate,
-                              0, st);
-}
-
-int zk_encode_responses3(const ZkRespBatch* r, const ZkNodeStore* s,
-                         const int64_t* n_dev, int64_t ncap, int64_t* sizes,
-                         int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                         uint8_t* out, int64_t out_cap, int32_t* err,
-                         int32_t presized, int32_t terminate, int64_t stage_req,
-                         hipStream_t st) {
+int zk_encode_responses(const ZkRespBatch* r, const ZkNodeStore* s,
+                        const int64_t* n_dev, int64_t ncap, int64_t* sizes,
+                        int64_t* rec_off, int64_t* total, int64_t* scan_ws,
+                        uint8_t* out, int64_t out_cap, int32_t* err,
+                        int32_t presized, int32_t terminate, hipStream_t st) {
   if (ncap <= 0) {
     int rc = hipMemsetAsync(total, 0, 8, st);
     if (!rc) rc = hipMemsetAsync(err, 0, 4, st);
@@ -1194,38 +1060,17 @@ int zk_encode_responses3(const ZkRespBatch* r, const ZkNodeStore* s,
   }
   // presized == 2: the block bases and *total are already in place
   // (zk_tree_finish_scan scanned the serve's block sums)
-  const bool fused = presized != 2 && nb <= zk::FUSED_SCAN_BLOCKS &&
-                     zk::enc_fused();
-  if (!fused && presized != 2) {
+  if (presized != 2) {
     int rc = zk_scan_small_i64(bsum, bbase, nb, total, st);
     if (rc) return rc;
   }
-  // reply image per workgroup (a 56 KiB image gained 0.5 % on 0-1024 B
-  // payloads and cost GET 2 %)
-  // (at least the uniform writer's header table and a few records' image)
-  const int64_t stage = stage_req <= 0 ? zk::STAGE_BYTES
-                        : stage_req < 8192 ? 8192
-                        : stage_req > zk::STAGE_BYTES ? zk::STAGE_BYTES
-                                                      : (stage_req + 15) & ~15;
-  if (zk::enc_swz() == 1)
-    zk::resp_write<1><<<nb, zk::ENC_T, (size_t)stage, st>>>(
-        *r, *s, n_dev, ncap, sizes, bbase, fused ? bsum : nullptr, rec_off,
-        total, out, out_cap, err, terminate, stage, zk::enc_uniform());
-  else
-    zk::resp_write<0><<<nb, zk::ENC_T, (size_t)stage, st>>>(
-        *r, *s, n_dev, ncap, sizes, bbase, fused ? bsum : nullptr, rec_off,
-        total, out, out_cap, err, terminate, stage, zk::enc_uniform());
+  // reply image per workgroup: STAGE_BYTES (a 56 KiB image gained 0.5 % on
+  // 0-1024 B payloads and cost GET 2 %)
+  zk::resp_write<<<nb, zk::ENC_T, zk::STAGE_BYTES, st>>>(
+      *r, *s, n_dev, ncap, sizes, bbase, rec_off, total, out, out_cap, err,
+      terminate, zk::enc_uniform());
   ZK_LAUNCH_CHECK();
   return 0;
-}
-
-int zk_encode_responses(const ZkRespBatch* r, const ZkNodeStore* s,
-                        const int64_t* n_dev, int64_t ncap, int64_t* sizes,
-                        int64_t* rec_off, int64_t* total, int64_t* scan_ws,
-                        uint8_t* out, int64_t out_cap, int32_t* err,
-                        hipStream_t st) {
-  return zk_encode_responses2(r, s, n_dev, ncap, sizes, rec_off, total,
-                              scan_ws, out, out_cap, err, 0, 0, st);
 }
 
 }  // extern "C"

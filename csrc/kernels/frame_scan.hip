@@ -86,17 +86,9 @@ constexpr int FL_U = 8;                    // fs_link loads per batch
 // fs_link's grid words (see fl_check's caller)
 constexpr int FL_NB = 2;                   // broken links the check saw
 constexpr int FL_GW = FL_NB + 1;
-constexpr int FL_LOC = 1024;               // a block's own broken links
 constexpr int FL_BROUNDS = 8;             // the last block's repair rounds
 constexpr int FL_DBG_BLOCKS = 16;          // fs_link blocks with a debug clock
 constexpr int FL_DBG_ROWS = 6;             // fs_link's debug rows past the tiles
-// A block's own round over the broken links it found, before its ticket:
-// off (the threshold is past any count).  Measured with the threshold at 64
-// (tools/microbench/fl_probe.py, profiles/r5_fs_link_ab.md): the phantom-chain
-// stream 0.69 ms a scan (one block walked 82 tiles serially before the last
-// block could chase the region), 0.27 ms without; the dense and no-spec
-// streams the same either way.
-constexpr int FL_LOCAL_MIN = 1 << 30;
 // The last block's one exact chase before its rounds (many broken links):
 // tiles it may walk before it leaves the rest to the rounds
 constexpr uint32_t FL_CHASE_WALKS = 16;
@@ -1777,16 +1769,11 @@ ZK_DEV FcWalk fc_walk(const uint8_t* __restrict__ buf, int64_t n,
 // broken link with the exact entry — one wave looks a run of tiles up in
 // fs_tile's candidate exits 64 at a time, walking only the tiles whose
 // exact entry is not a candidate — until every live link holds.
-// Before its ticket, a block re-walks the broken links its own check found
-// (one wave a link, from the exit before it as recorded; fl_accept's rule),
-// one parallel repair round over the whole grid without any barrier: a
-// tile whose speculated entry was missing or wrong but whose survivor is
-// the true chain (every tile of a `nospec` stream, a frontier wait that
-// timed out) re-walks to the same exit, so the round settles any number of
-// such tiles at once — the last block then only checks and re-counts.
-// Grid words (LW_GRID, uint64): [0] the ticket, [1] tiles the blocks
-// re-walked, [FL_NB] the check's count of broken links (fs_rows clears it
-// for the next scan).
+// (A block re-walking the broken links its own check found before its
+// ticket lost: the phantom-chain scan 0.27 -> 0.69 ms,
+// profiles/r5_fs_link_ab.md.)
+// Grid words (LW_GRID, uint64): [0] the ticket, [1] unused, [FL_NB] the
+// check's count of broken links (fs_rows clears it for the next scan).
 // At most this many broken links: chased from the check's list (fl_chase; a
 // reply stream usually has a handful of broken links or none); more go to
 // the tail's exact chases.
@@ -1823,8 +1810,8 @@ ZK_DEV bool fl_accept(const int64_t* rec_entry, const int64_t* rec_exit,
   return ld_agent(&rec_entry[k + 1]) != ox;
 }
 
-// The block's repair round (see FL_LOC): its check's broken links, one wave
-// a link.  Returns the tiles this wave re-walked.
+// A repair round of the last block: the broken links lloc[0, nloc), one
+// wave a link.  Returns the tiles this wave re-walked.
 ZK_DEV uint32_t fl_local_round(const uint8_t* __restrict__ buf, int64_t n,
                                int64_t ntiles, int64_t maxp,
                                const int64_t* __restrict__ sx,
@@ -1993,8 +1980,6 @@ ZK_DEV bool fl_round(const uint8_t* __restrict__ buf, int64_t n,
 }
 
 // The full check (fs_link, when fs_tile counted a bad link): every link and
-
-// The full check (fs_link, when fs_tile counted a bad link): every link and
 // terminal, one wave per count block of FK_T tiles over the grid, and the
 // frame counts scanned per block: base[k] = count before tile k within its
 // block, bsum[b] = the block's total.  The leftmost broken link and terminal
@@ -2005,8 +1990,7 @@ ZK_DEV void fl_check(int64_t ntiles, const int64_t* __restrict__ rec_entry,
                      const int64_t* __restrict__ rec_exit,
                      const int64_t* __restrict__ rec_meta, int64_t* base,
                      int64_t* bsum, uint64_t* mins,
-                     unsigned long long* nbroken, int32_t* blist,
-                     int32_t* lloc, int* lcnt) {
+                     unsigned long long* nbroken, int32_t* blist) {
   const int lane = threadIdx.x & 63;
   const int64_t INF = INT64_MAX;
   const int64_t nw = (int64_t)gridDim.x * (FL_T / 64);
@@ -2036,15 +2020,10 @@ ZK_DEV void fl_check(int64_t ntiles, const int64_t* __restrict__ rec_entry,
       unsigned long long b0 = 0;
       if (lane == 0) b0 = atomicAdd(nbroken, (unsigned long long)__popcll(bm));
       b0 = __shfl(b0, 0, 64);
-      int l0 = 0;
-      if (lane == 0) l0 = atomicAdd(lcnt, __popcll(bm));
-      l0 = __shfl(l0, 0, 64);
       if (brk) {
         const uint64_t below = lane ? (bm & ((~0ull) >> (64 - lane))) : 0ull;
         __hip_atomic_store(&blist[b0 + __popcll(below)], (int32_t)(k + 1),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int li = l0 + __popcll(below);
-        if (li < FL_LOC) lloc[li] = (int32_t)(k + 1);
       }
     }
     int64_t inc = cnt;
@@ -2704,7 +2683,7 @@ __global__ __launch_bounds__(FL_T) void fs_link(
     int64_t* __restrict__ bsum, uint64_t* mins,
     int64_t* __restrict__ lastk, unsigned long long* g,
     const uint64_t* lbw, const int64_t* __restrict__ cx,
-    int64_t* __restrict__ ldbg, int32_t local_min, int32_t fflags) {
+    int64_t* __restrict__ ldbg) {
   __shared__ __attribute__((aligned(16)))
       uint8_t win[(FL_T / 64) * (FC_WIN + 16)];      // one per wave
   __shared__ int64_t red[2 * (FL_T / 64) + 2];
@@ -2722,16 +2701,11 @@ __global__ __launch_bounds__(FL_T) void fs_link(
   const int64_t INF = INT64_MAX;
   const int64_t t_in = ldbg != nullptr ? wall_clock64() : 0;
   // the check over the grid (links, terminals, in-block counts; a launch of
-  // its own until round 4), the block's repair round over the broken links
-  // it found, then a ticket: the last block to take one sees every block's
-  // check and repairs (each releases them before its ticket) and goes on
+  // its own until round 4), then a ticket: the last block to take one sees
+  // every block's check (each releases it before its ticket) and goes on
   // alone; the others are done
-  __shared__ int32_t lloc[FL_LOC];
-  __shared__ int s_lcnt;
-  if (tid == 0) s_lcnt = 0;
-  __syncthreads();
   fl_check(ntiles, rec_entry, rec_exit, rec_meta, base, bsum, mins, &g[FL_NB],
-           blist, lloc, &s_lcnt);
+           blist);
   if (ldbg != nullptr && tid == 0 && blockIdx.x < FL_DBG_BLOCKS) {
     // (ZKMI_FS_DBG: every block's entry and check-done clocks, rows 1-4 of
     // fs_link's debug rows)
@@ -2755,20 +2729,10 @@ __global__ __launch_bounds__(FL_T) void fs_link(
       for (int r = 0; r < FL_GROUNDS; ++r) gb[4 + 2 * r] = 0;
     }
   }
-  __syncthreads();
-  // (a handful of broken links — a frontier timeout, a garbage candidate,
-  // the ends of a phantom chain's region — are the last block's chases:
-  // an exact chase runs on through a region of consistent-but-wrong links
-  // that no per-link walk sees broken)
-  if (!big && s_lcnt > local_min) {
-    const uint32_t w = fl_local_round(buf, n, ntiles, maxp, sx, list, rcount,
-                                      pre, rec_entry, rec_exit, rec_meta, lloc,
-                                      min(s_lcnt, FL_LOC), win);
-    if (lane == 0 && w) {
-      fc_stat(stats, 2, w);
-      atomicAdd(&g[1], (unsigned long long)w);
-    }
-  }
+  // (the broken links — a frontier timeout, a garbage candidate, the ends
+  // of a phantom chain's region — are all the last block's: an exact chase
+  // runs on through a region of consistent-but-wrong links that no per-link
+  // walk sees broken)
   __shared__ int s_last;
   __syncthreads();
   if (big) {
@@ -2788,27 +2752,22 @@ __global__ __launch_bounds__(FL_T) void fs_link(
   __syncthreads();
   if (!s_last) return;
   // the minima and the broken-link count (fs_rows clears them for the next
-  // scan of this workspace), and the tiles the blocks' rounds re-walked
+  // scan of this workspace)
   const uint64_t mb0 = ld_agent((const int64_t*)&mins[0]);
   const uint64_t mt0 = ld_agent((const int64_t*)&mins[1]);
   const unsigned long long nb0 = __hip_atomic_load(
       &g[FL_NB], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long rew = __hip_atomic_load(
-      &g[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int64_t fb0 = mb0 ? ntiles - (int64_t)mb0 : INF;
   const int64_t ft0 = mt0 ? ntiles - (int64_t)mt0 : INF;
   if (!big && (fb0 == INF || fb0 > ft0)) {
-    // no broken link before the first terminal (the blocks re-walked only
-    // links past it, whose counts no row uses): the row bases are bsum's
+    // no broken link before the first terminal: the row bases are bsum's
     // block offsets + the check's in-block bases
     if (ldbg != nullptr && tid == 0) ldbg[40] = wall_clock64();
     fl_bases(n, ntiles, ft0, rec_exit, rec_meta, base, bsum, cap, result,
              lastk, red);
-    if (tid == 0 && rew) g[1] = 0;
     if (ldbg != nullptr && tid == 0) ldbg[41] = wall_clock64();
     return;
   }
-  if (tid == 0) g[1] = 0;
   __shared__ uint32_t dirty[FL_DB / 32];
   __shared__ int s_ovf;
   FlChase ch{dirty, &s_ovf, stats, ldbg};
@@ -2823,11 +2782,11 @@ __global__ __launch_bounds__(FL_T) void fs_link(
   int64_t nb = (int64_t)nb0;
   // repair rounds of this block: a handful of broken links are chased (the
   // usual repair: one pass, then only the count blocks it touched are
-  // re-counted); many are re-walked in parallel, one wave a link (the
-  // blocks' round continued here); after each, the links still broken are
-  // listed again.  What the rounds leave goes to the tail.
-  bool changed = rew != 0 || big;       // records changed beyond the chases' dirty
-  if (!big && nb > (int64_t)FL_SMALL && fb0 != INF && (fflags & 1)) {
+  // re-counted); many are re-walked in parallel, one wave a link; after
+  // each, the links still broken are listed again.  What the rounds leave
+  // goes to the tail.
+  bool changed = big;          // records changed beyond the chases' dirty
+  if (!big && nb > (int64_t)FL_SMALL && fb0 != INF) {
     // many broken links: first ONE exact chase from the leftmost, wave 0,
     // through fs_tile's candidate exits 64 tiles a batch.  A stream whose
     // every frame carries a phantom chain of the frame's own period (SET_DATA
@@ -2977,7 +2936,7 @@ __global__ __launch_bounds__(256) void fs_rows(
   }
   if (t * FT_S >= n) return;
   // the scan is over for this tile: clear its candidate flags, so the next
-  // scan of this workspace needs no memset (zk_frame_scan4 clean=1)
+  // scan of this workspace needs no memset (zk_frame_scan clean=1)
   if (lane == 0) {
     lbw[2 * t] = 0;
     lbw[2 * t + 1] = 0;
@@ -3074,16 +3033,6 @@ __global__ __launch_bounds__(64) void fs_small(
   }
 }
 
-// ZKMI_FS_SMALL=0: one-tile streams take the tiled scan too (A/B)
-static bool fs_small_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ZKMI_FS_SMALL");
-    v = (e ? atoi(e) : 1) ? 1 : 0;
-  }
-  return v != 0;
-}
-
 struct FsPlan {
   int64_t tiles;
   size_t off_list, off_pre, off_sx, off_lbw, off_rent, off_rexit, off_rmeta,
@@ -3113,28 +3062,6 @@ static FsPlan fs_plan(int64_t n) {
   return p;
 }
 
-// A block re-walks its own broken links before its ticket when it found
-// more than this many (ZKMI_FL_LOCAL_MIN overrides FL_LOCAL_MIN, for A/B)
-static int32_t fl_local_min() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ZKMI_FL_LOCAL_MIN");
-    v = e ? atoi(e) : FL_LOCAL_MIN;
-  }
-  return v;
-}
-
-// fs_link's switches: bit 0 the exact chase before the rounds
-// (ZKMI_FL_CHASE_FIRST=0 turns it off, for A/B)
-static int32_t fl_flags() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ZKMI_FL_CHASE_FIRST");
-    v = (e ? atoi(e) : 1) ? 1 : 0;
-  }
-  return v;
-}
-
 // fs_link's grid: the check's workgroups (the last to finish goes on).
 static unsigned fl_blocks() { return 16; }
 
@@ -3151,15 +3078,10 @@ constexpr int32_t FS_LONG = 2;
 // it when the window is below the stream's largest frame)
 constexpr int32_t FS_WIN_LONG = 1 << 16;
 
-static int fs_tpb() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ZKMI_FS_TPB");
-    const int x = e ? atoi(e) : 4;
-    v = (x == 1 || x == 2) ? x : 4;
-  }
-  return v;
-}
+// fs_tile's tiles (waves) per block: four 12 KiB slices, 3 blocks a CU (as
+// many waves as two-slice blocks, half the workgroups to dispatch: GET 0.585
+// -> 0.581 ms, mix and watch -0.7 %, profiles/r5_fs_tpb_ab.log)
+constexpr int FS_TPB = 4;
 
 static int fs_window(int32_t window) {
   window &= FS_WIN_LONG - 1;
@@ -3224,10 +3146,10 @@ int64_t zk_frame_scan_workspace(int64_t n) {
 // below the stream's largest frame: fs_tile's frontier passes); tests of
 // the link repair: bit 0 no speculated tile entries; bits 8..23 P > 0:
 // every P-th tile (t % P == 1) takes a garbage entry.
-int zk_frame_scan5(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
-                   int64_t maxp, uint8_t* ws, int64_t ws_bytes, int64_t* foff,
-                   int32_t* flen, int64_t cap, int64_t* result, int32_t window,
-                   int32_t clean, int32_t flags, hipStream_t st) {
+int zk_frame_scan(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
+                  int64_t maxp, uint8_t* ws, int64_t ws_bytes, int64_t* foff,
+                  int32_t* flen, int64_t cap, int64_t* result, int32_t window,
+                  int32_t clean, int32_t flags, hipStream_t st) {
   using namespace zk;
   const int W = fs_window(window);
   if (window & FS_WIN_LONG) flags |= FS_LONG;
@@ -3235,7 +3157,7 @@ int zk_frame_scan5(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
   FsPlan p = fs_plan(n_cap);
   if ((int64_t)p.total > ws_bytes) return -1;
   const int64_t tiles = p.tiles;
-  if (n_cap <= FT_S && !(flags & (1 | 0xFFFF00)) && fs_small_on() &&
+  if (n_cap <= FT_S && !(flags & (1 | 0xFFFF00)) &&
       fs_dbg_buf(tiles) == nullptr) {
     fs_small<<<1, 64, 0, st>>>(buf, n_dev, n_cap, maxp, foff, flen, cap,
                                result);
@@ -3264,20 +3186,13 @@ int zk_frame_scan5(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
           hipSuccess)
     return -4;
   int64_t* dbg = fs_dbg_buf(tiles);
-  // tiles (waves) per block: four 12 KiB slices, 3 blocks a CU (as many
-  // waves as two-slice blocks, half the workgroups to dispatch: GET 0.585
-  // -> 0.581 ms, mix and watch -0.7 %, profiles/r5_fs_tpb_ab.log).  (One
-  // 23 ms watch step seen once in a full-suite process was a host pause
-  // between the test's event records — the collector — not K1: six full
-  // and isolated runs since, either width, show none.)  ZKMI_FS_TPB = 1 /
-  // 2 / 4 for A/B runs.
-  const int tpb = fs_tpb();
+  constexpr int tpb = FS_TPB;
   // tiles a wave: groups (the map once, the chain walked on) for streams
   // of large frames within a small window; tests of the link repair and
   // long-frame streams take single tiles
   int G = ((flags >> 4) & 15) + 1;
   if ((flags & (FS_LONG | 1 | 0xFFFF00)) || W > 512) G = 1;
-  G = G >= 16 ? 16 : G >= 8 ? 8 : G >= 4 ? 4 : G >= 2 ? 2 : 1;
+  G = G >= 8 ? 8 : G >= 4 ? 4 : G >= 2 ? 2 : 1;
   const int64_t waves = (tiles + G - 1) / G;
   const unsigned tblocks = (unsigned)((waves + tpb - 1) / tpb);
 #define ZK_FS_TILE(WW, LL)                                                   \
@@ -3288,10 +3203,7 @@ int zk_frame_scan5(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
   fs_tile<WW, false, GG><<<tblocks, 64 * tpb, FT_LDS * tpb, st>>>(           \
       buf, n_dev, n_cap, maxp, list, pre, sx, lbw, rent, rexit, rmeta, rcnt, \
       tiles, dbg, fs_minb(), flags, cx)
-  if (G == 16) {
-    if (W == 256) ZK_FS_GROUP(256, 16);
-    else ZK_FS_GROUP(512, 16);
-  } else if (G == 8) {
+  if (G == 8) {
     if (W == 256) ZK_FS_GROUP(256, 8);
     else ZK_FS_GROUP(512, 8);
   } else if (G == 4) {
@@ -3321,30 +3233,13 @@ int zk_frame_scan5(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
   fs_link<<<fl_blocks(), FL_T, 0, st>>>(buf, n_dev, n_cap, maxp, sx, list, rcnt,
                                  pre, rent, rexit, rmeta, base, cap, result,
                                  lbw + 2 * tiles, blist, bsum, mins, lastk,
-                                 grid, lbw, cx, dbg ? dbg + 8 * tiles : nullptr,
-                                 fl_local_min(), fl_flags());
+                                 grid, lbw, cx, dbg ? dbg + 8 * tiles : nullptr);
   ZK_LAUNCH_CHECK();
   fs_rows<<<(unsigned)((tiles + 3) / 4), 256, 0, st>>>(
       buf, n_dev, n_cap, list, pre, rmeta, rent, rexit, base, bsum, lastk,
       foff, flen, cap, lbw, lbw + 2 * tiles);
   ZK_LAUNCH_CHECK();
   return 0;
-}
-
-int zk_frame_scan4(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
-                   int64_t maxp, uint8_t* ws, int64_t ws_bytes, int64_t* foff,
-                   int32_t* flen, int64_t cap, int64_t* result, int32_t window,
-                   int32_t clean, hipStream_t st) {
-  return zk_frame_scan5(buf, n_dev, n_cap, maxp, ws, ws_bytes, foff, flen,
-                        cap, result, window, clean, 0, st);
-}
-
-int zk_frame_scan3(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
-                   int64_t maxp, uint8_t* ws, int64_t ws_bytes, int64_t* foff,
-                   int32_t* flen, int64_t cap, int64_t* result, int32_t window,
-                   hipStream_t st) {
-  return zk_frame_scan4(buf, n_dev, n_cap, maxp, ws, ws_bytes, foff, flen, cap,
-                        result, window, 0, st);
 }
 
 // Chain statistics of the last scan of workspace `ws` over a buffer of
@@ -3379,20 +3274,6 @@ int zk_frame_scan_dbg(int64_t* host, int64_t tiles) {
   if (!zk::g_dbg || tiles > zk::g_dbg_tiles + zk::FL_DBG_ROWS) return -1;
   return hipMemcpy(host, zk::g_dbg, tiles * 8 * 8, hipMemcpyDeviceToHost) ==
                  hipSuccess ? 0 : -1;
-}
-
-int zk_frame_scan2(const uint8_t* buf, int64_t n, int64_t maxp, uint8_t* ws,
-                   int64_t ws_bytes, int64_t* foff, int32_t* flen, int64_t cap,
-                   int64_t* result, int32_t window, hipStream_t st) {
-  return zk_frame_scan3(buf, nullptr, n, maxp, ws, ws_bytes, foff, flen, cap,
-                        result, window, st);
-}
-
-int zk_frame_scan(const uint8_t* buf, int64_t n, int64_t maxp, uint8_t* ws,
-                  int64_t ws_bytes, int64_t* foff, int32_t* flen, int64_t cap,
-                  int64_t* result, hipStream_t st) {
-  return zk_frame_scan3(buf, nullptr, n, maxp, ws, ws_bytes, foff, flen, cap,
-                        result, 2048, st);
 }
 
 }  // extern "C"

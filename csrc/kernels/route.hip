@@ -320,10 +320,6 @@ extern "C" {
 
 // int64 scratch a route of n requests over `world` ranks needs: the
 // histogram, its scan, the scan total and the scan workspace.
-int64_t zk_route_workspace(int64_t n, int32_t world);
-
-int64_t zk_scan_workspace(int64_t n);
-
 int64_t zk_route_workspace(int64_t n, int32_t world) {
   const int64_t nblk = (n + zk::RT_T - 1) / zk::RT_T;
   const int64_t m = nblk * world;
@@ -333,29 +329,12 @@ int64_t zk_route_workspace(int64_t n, int32_t world) {
 // Route n request descriptors (idx, xid, path off/len) to `world` owners:
 // writes owner[n], the owner-grouped descriptors (*_s) and counts[world].
 // self: the groups in rotation order from owner self (route_owner_k).
-int zk_route_requests2(int64_t n, int32_t world, int32_t self,
-                       const int64_t* poff, const int32_t* plen,
-                       const uint8_t* arena, const int64_t* idx,
-                       const int32_t* xid, int32_t* owner, int64_t* idx_s,
-                       int32_t* xid_s, int64_t* poff_s, int32_t* plen_s,
-                       int64_t* counts, int64_t* ws, hipStream_t st);
-
-int zk_route_requests(int64_t n, int32_t world, const int64_t* poff,
-                      const int32_t* plen, const uint8_t* arena,
-                      const int64_t* idx, const int32_t* xid, int32_t* owner,
-                      int64_t* idx_s, int32_t* xid_s, int64_t* poff_s,
-                      int32_t* plen_s, int64_t* counts, int64_t* ws,
-                      hipStream_t st) {
-  return zk_route_requests2(n, world, 0, poff, plen, arena, idx, xid, owner,
-                            idx_s, xid_s, poff_s, plen_s, counts, ws, st);
-}
-
-int zk_route_requests2(int64_t n, int32_t world, int32_t self,
-                       const int64_t* poff, const int32_t* plen,
-                       const uint8_t* arena, const int64_t* idx,
-                       const int32_t* xid, int32_t* owner, int64_t* idx_s,
-                       int32_t* xid_s, int64_t* poff_s, int32_t* plen_s,
-                       int64_t* counts, int64_t* ws, hipStream_t st) {
+int zk_route_requests(int64_t n, int32_t world, int32_t self,
+                      const int64_t* poff, const int32_t* plen,
+                      const uint8_t* arena, const int64_t* idx,
+                      const int32_t* xid, int32_t* owner, int64_t* idx_s,
+                      int32_t* xid_s, int64_t* poff_s, int32_t* plen_s,
+                      int64_t* counts, int64_t* ws, hipStream_t st) {
   if (world < 1 || world > zk::RT_MAXW || self < 0 || self >= world)
     return (int)hipErrorInvalidValue;
   if (n <= 0) return hipMemsetAsync(counts, 0, sizeof(int64_t) * world, st);

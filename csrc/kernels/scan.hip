@@ -24,8 +24,6 @@
 #include "zk_common.h"
 #include "zk_mfma_scan.h"
 
-#include <stdlib.h>
-
 namespace zk {
 
 constexpr int SCAN_T = 256;
@@ -181,19 +179,6 @@ __global__ __launch_bounds__(NT) void scan_one_block_mfma(
   if (total != nullptr && threadIdx.x == 0) *total = t;
 }
 
-// ZKMI_SMALL_SCAN: the engine of the one-workgroup scans (zk_scan_small_i64:
-// K10 / K13's block sums; tree_finish_scan): "shfl" (default) or "mfma".
-// The MFMA version costs the GET step 2.6 % (profiles/r6_mfma_ab.md): a
-// 2048-value scan is latency, not arithmetic.
-static int small_scan_mode() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("ZKMI_SMALL_SCAN");
-    v = (e != nullptr && e[0] == 'm') ? 1 : 0;
-  }
-  return v;
-}
-
 template <typename T>
 static int scan_rec(const T* in, int64_t* out, int64_t n, int64_t* total,
                     int64_t* ws, hipStream_t st);
@@ -294,8 +279,8 @@ int64_t zk_scan_workspace(int64_t n) {
   return w + 2 > enc ? w + 2 : enc;
 }
 
-// Exclusive scan of n values (any n) by one workgroup, one launch: the
-// encoders' block sums.
+// Exclusive scan of n values (any n) by one workgroup, one launch, with an
+// explicit engine (1 MFMA, 0 shuffle; the tests run both).
 int zk_scan_small_i64_mode(const int64_t* in, int64_t* out, int64_t n,
                            int64_t* total, int mode, hipStream_t st) {
   if (n <= 0) {
@@ -310,14 +295,13 @@ int zk_scan_small_i64_mode(const int64_t* in, int64_t* out, int64_t n,
   return 0;
 }
 
+// The encoders' block sums (K10 / K13): the shuffle engine.  The MFMA one
+// costs the GET step 2.6 % (profiles/r6_mfma_ab.md): a 2048-value scan is
+// latency, not arithmetic.
 int zk_scan_small_i64(const int64_t* in, int64_t* out, int64_t n,
                       int64_t* total, hipStream_t st) {
-  return zk_scan_small_i64_mode(in, out, n, total, zk::small_scan_mode(), st);
+  return zk_scan_small_i64_mode(in, out, n, total, 0, st);
 }
-
-// The one-workgroup scan's engine (1 = MFMA, 0 = shuffle), for
-// tree_finish_scan (tree.hip) and the tests.
-int zk_scan_small_mode(void) { return zk::small_scan_mode(); }
 
 // 0 = shuffle engine, 1 = MFMA byte-plane engine; returns the old mode.
 // 2 / 3 force one-wave / four-wave MFMA blocks (auto picks by n); 4 the

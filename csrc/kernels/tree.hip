@@ -42,7 +42,6 @@
 // write request is assigned a zxid, failed ones included (ZooKeeper logs an
 // error txn for them).
 #include "zk_common.h"
-#include "zk_mfma_scan.h"
 #include "zk_reqparse.h"
 
 namespace zk {
@@ -742,7 +741,7 @@ __global__ __launch_bounds__(TR_T) void tree_fill_k(ZkTree t, int64_t n0,
 
 // Free-ring compaction between batches: the ring's pending entries rebuilt
 // as every free node in ascending order.  Frees go to the ring in the
-// order the workgroups of a batch happened to take their tickets, and
+// order the workgroups of a batch happened to take their ticket, and
 // creates take the ring in ticket order too, so over a few hundred batches
 // of create / delete the nodes one workgroup creates scatter over the whole
 // node table (each per-node field a random line instead of a shared one):
@@ -929,15 +928,11 @@ ZK_DEV int32_t do_create(const ZkTree& t, Lane& L, const uint8_t* data,
 // path arena (SEQUENTIAL names differ from the requested one).  r_slot,
 // r_sizes and r_bsum (may be null) receive each reply's slot offset, its
 // frame size and the block's size sum, so the reply encoder needs neither
-// its sizes pass nor a lookup of the node's slot (zk_encode_responses2
+// its sizes pass nor a lookup of the node's slot (zk_encode_responses
 // presized).
 // PARSE: the requests come as K1 frames (foff / flen) and each lane parses
 // its own in registers (zk_reqparse.h) instead of reading K12's SoA back —
 // one launch and a 30 MB write + read less per 512K-request batch.
-ZK_DEV void finish_body(const ZkTree& t, const int64_t* n_dev,
-                        int64_t bump_zxid, int32_t publish);
-ZK_DEV bool serve_last(unsigned* tickets);
-
 // RO: a batch of reads only (GET_DATA / EXISTS; the GET pipeline's): no
 // node / storage claims, frees or dirty parents, so none of their five
 // block-wide ticket barriers per workgroup; any other op is answered
@@ -955,7 +950,7 @@ __global__ __launch_bounds__(TR_T) void tree_serve_k(
     int64_t* __restrict__ r_bsum, int64_t session, int64_t now_ms,
     const uint8_t* __restrict__ rank, int32_t pass, int32_t last_pass,
     int64_t snap_base, int64_t snap_cap, int64_t* __restrict__ snap_top,
-    int32_t wslot, int64_t* __restrict__ fired, unsigned* tickets) {
+    int32_t wslot, int64_t* __restrict__ fired) {
   session = sess_of(t, session);
   const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);
   const int64_t i = (int64_t)blk * TR_T + threadIdx.x;
@@ -1227,9 +1222,6 @@ __global__ __launch_bounds__(TR_T) void tree_serve_k(
     block_excl_scan(sz, sm, &tot);
     if (threadIdx.x == 0) r_bsum[blk] = tot;
   }
-  // the finish in the launch's last workgroup (no tree_finish_k launch)
-  if (tickets != nullptr && serve_last(tickets))
-    finish_body(t, n_dev, 0, 1);
   if (!live) return;
   r_op[i] = L.op;
   r_xid[i] = rq.xid;
@@ -2132,8 +2124,7 @@ constexpr int FIN_T = 1024;
 // cross-block sign-off — the grid version's atomic sign-off counter took
 // 15-60 us per launch on a read-only GET batch, and two streams finishing
 // at once could interleave on it.
-// The finish (see above) by the calling workgroup (blockDim.x threads):
-// tree_finish_k's launch, or the serve launch's last workgroup (serve_last).
+// The finish (see above) by the calling workgroup (blockDim.x threads).
 // The counters and parent shadows other workgroups updated are read with
 // agent-scope loads (this workgroup's L1 may hold older lines).
 ZK_DEV void finish_body(const ZkTree& t, const int64_t* n_dev,
@@ -2180,22 +2171,14 @@ __global__ __launch_bounds__(NT) void tree_finish_k(ZkTree t,
 // scan_one_block), each waiting for a CU behind the other connection's
 // kernels.  Workgroup 1 scans the serve's per-256-reply size sums (bsum,
 // nb of them) into the encoder's block bases and writes the stream total
-// (zk_encode_responses3 `prescanned`).
-// MFMA: workgroup 1 scans on the matrix cores (zk_mfma_scan.h: 2048 block
-// sums of a 512K-reply connection are one 4096-value chunk of four waves).
-template <int NT, bool MFMA>
+// (zk_encode_responses `presized` 2).
+template <int NT>
 __global__ __launch_bounds__(NT) void tree_finish_scan_k(
     ZkTree t, const int64_t* n_dev, int64_t bump_zxid, int32_t publish,
     const int64_t* __restrict__ bsum, int64_t nb, int64_t* __restrict__ bbase,
     int64_t* __restrict__ total) {
   if (blockIdx.x == 0) {
     finish_body(t, n_dev, bump_zxid, publish);
-    return;
-  }
-  if (MFMA) {
-    __shared__ int64_t wsum[NT / 64 + 1];
-    const int64_t tot = mfma_scan_block_direct<NT>(bsum, nb, bbase, wsum);
-    if (threadIdx.x == 0) *total = tot;
     return;
   }
   // a thread owns FS_V consecutive sums, so a 512K-reply connection's 2048
@@ -2223,38 +2206,6 @@ __global__ __launch_bounds__(NT) void tree_finish_scan_k(
     carry += tot;
   }
   if (threadIdx.x == 0) *total = carry;
-}
-
-// Is this the serve launch's last workgroup to finish?  Tickets in groups
-// of 64 workgroups (tickets[1 + g]; the last of a group takes one of
-// tickets[0]), so no counter takes more than 64 atomics — one counter
-// for a whole grid (thousands of same-address atomics) took 15-60 us a
-// launch.  The counters are the caller's (one set per server: two
-// connections serving one tree at once keep apart) and are left zero.
-ZK_DEV bool serve_last(unsigned* tickets) {
-  __shared__ int s_last;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const unsigned ng = (gridDim.x + 63) / 64;
-    const unsigned g = blockIdx.x / 64;
-    const unsigned gs = min(64u, gridDim.x - g * 64);
-    int last = 0;
-    if (atomicAdd(&tickets[1 + g], 1u) + 1 == gs) {
-      __hip_atomic_store(&tickets[1 + g], 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence();
-      if (atomicAdd(&tickets[0], 1u) + 1 == ng) {
-        __hip_atomic_store(&tickets[0], 0u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        last = 1;
-      }
-    }
-    __threadfence();
-    s_last = last;
-  }
-  __syncthreads();
-  return s_last != 0;
 }
 
 // Session expiry: remove every ephemeral node owned by `session`
@@ -2570,7 +2521,7 @@ int zk_tree_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
                             zk::TR_T, 0, st>>>(
       *t, rx, *q, nullptr, nullptr, n_dev, ncap, r_op, r_xid, r_err, r_node,
       r_zxid, r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session,
-      now_ms, nullptr, 0, 1, 0, 0, nullptr, -1, nullptr, nullptr);
+      now_ms, nullptr, 0, 1, 0, 0, nullptr, -1, nullptr);
   ZK_LAUNCH_CHECK();
   // at most one dirty parent per request
   return finish_launch(t, ncap, n_dev, 0, st);
@@ -2578,50 +2529,11 @@ int zk_tree_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
 
 // zk_tree_serve straight from K1's frame table (foff / flen, *n_dev
 // frames): every lane parses its request in registers (no K12 pass).
-// tickets (may be null; zk_serve_tickets(ncap) zeroed uint32, kept per
-// server): the launch's last workgroup does the finish (serve_last), no
-// tree_finish_k launch.
 // wslot: this session's watcher slot (-1: its reads arm no watch); fired
 // (may be null; [ncap * 5]): per successful write, the watcher masks it
 // fired and the paths (zk_watch_events expands them).
-int64_t zk_serve_tickets(int64_t ncap) {
-  const int64_t nb = (ncap + zk::TR_T - 1) / zk::TR_T;
-  return 1 + (nb + 63) / 64;
-}
-
-// finish: ZK_SERVE_FINISH (else no finish at all: the caller launches
-// zk_tree_finish or zk_tree_finish_scan) | ZK_SERVE_RO (a batch of GET_DATA
-// / EXISTS only: tree_serve_k's RO instance)
-int zk_tree_serve_frames2(const ZkTree* t, const uint8_t* rx,
-                          const int64_t* foff, const int32_t* flen,
-                          const int64_t* n_dev, int64_t ncap, int32_t* r_op,
-                          int32_t* r_xid, int32_t* r_err, int64_t* r_node,
-                          int64_t* r_zxid, int64_t* r_path_off,
-                          int32_t* r_path_len, int64_t* r_slot,
-                          int64_t* r_sizes, int64_t* r_bsum, int64_t session,
-                          int64_t now_ms, int32_t wslot, int64_t* fired,
-                          unsigned* tickets, int32_t finish, hipStream_t st) {
-  if (ncap <= 0) return 0;
-  if ((r_sizes == nullptr) != (r_bsum == nullptr)) return -1;
-  ZkReqOut none{};
-  const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
-  if (finish & ZK_SERVE_RO)
-    zk::tree_serve_k<true, true><<<nb, zk::TR_T, 0, st>>>(
-        *t, rx, none, foff, flen, n_dev, ncap, r_op, r_xid, r_err, r_node,
-        r_zxid, r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session,
-        now_ms, nullptr, 0, 1, 0, 0, nullptr, wslot, fired, tickets);
-  else
-    zk::tree_serve_k<true><<<nb, zk::TR_T, 0, st>>>(
-        *t, rx, none, foff, flen, n_dev, ncap, r_op, r_xid, r_err, r_node,
-        r_zxid, r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session,
-        now_ms, nullptr, 0, 1, 0, 0, nullptr, wslot, fired, tickets);
-  ZK_LAUNCH_CHECK();
-  // tickets: the serve launch's last workgroup did the finish
-  return tickets != nullptr || !(finish & ZK_SERVE_FINISH)
-             ? 0
-             : finish_launch(t, ncap, n_dev, 0, st);
-}
-
+// read_only: a batch of GET_DATA / EXISTS only (tree_serve_k's RO instance).
+// No finish: the caller launches zk_tree_finish_scan next.
 int zk_tree_serve_frames(const ZkTree* t, const uint8_t* rx,
                          const int64_t* foff, const int32_t* flen,
                          const int64_t* n_dev, int64_t ncap, int32_t* r_op,
@@ -2630,34 +2542,36 @@ int zk_tree_serve_frames(const ZkTree* t, const uint8_t* rx,
                          int32_t* r_path_len, int64_t* r_slot,
                          int64_t* r_sizes, int64_t* r_bsum, int64_t session,
                          int64_t now_ms, int32_t wslot, int64_t* fired,
-                         unsigned* tickets, hipStream_t st) {
-  return zk_tree_serve_frames2(t, rx, foff, flen, n_dev, ncap, r_op, r_xid,
-                               r_err, r_node, r_zxid, r_path_off, r_path_len,
-                               r_slot, r_sizes, r_bsum, session, now_ms, wslot,
-                               fired, tickets, ZK_SERVE_FINISH, st);
+                         int32_t read_only, hipStream_t st) {
+  if (ncap <= 0) return 0;
+  if ((r_sizes == nullptr) != (r_bsum == nullptr)) return -1;
+  ZkReqOut none{};
+  const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
+  if (read_only)
+    zk::tree_serve_k<true, true><<<nb, zk::TR_T, 0, st>>>(
+        *t, rx, none, foff, flen, n_dev, ncap, r_op, r_xid, r_err, r_node,
+        r_zxid, r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session,
+        now_ms, nullptr, 0, 1, 0, 0, nullptr, wslot, fired);
+  else
+    zk::tree_serve_k<true><<<nb, zk::TR_T, 0, st>>>(
+        *t, rx, none, foff, flen, n_dev, ncap, r_op, r_xid, r_err, r_node,
+        r_zxid, r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session,
+        now_ms, nullptr, 0, 1, 0, 0, nullptr, wslot, fired);
+  ZK_LAUNCH_CHECK();
+  return 0;
 }
 
 // The between-batch finish of a serve (parent Stat fix-up, free-ring
-// publish, zxid += *n_dev or bump) on its own: the partner of
-// zk_tree_serve_frames2(..., finish = 0).
-int zk_tree_finish(const ZkTree* t, const int64_t* n_dev, int64_t bump,
-                   int32_t publish, hipStream_t st) {
-  return finish_launch(t, 0, n_dev, bump, st, publish);
-}
-
-// zk_tree_finish + the presized reply encode's block-sum scan (the serve's
-// r_bsum for ncap replies, in scan_ws[0, nb)) -> scan_ws[nb, 2 nb) and
-// *total, in one launch (tree_finish_scan_k).
+// publish, zxid += *n_dev or bump), the partner of zk_tree_serve_frames, +
+// the presized reply encode's block-sum scan (the serve's r_bsum for ncap
+// replies, in scan_ws[0, nb)) -> scan_ws[nb, 2 nb) and *total, in one launch
+// (tree_finish_scan_k).
 int zk_tree_finish_scan(const ZkTree* t, const int64_t* n_dev, int64_t bump,
                         int32_t publish, int64_t ncap, int64_t* scan_ws,
                         int64_t* total, hipStream_t st) {
   const int64_t nb = ncap > 0 ? (ncap + 255) / 256 : 0;
-  if (zk_scan_small_mode() == 1)
-    zk::tree_finish_scan_k<256, true><<<2, 256, 0, st>>>(
-        *t, n_dev, bump, publish, scan_ws, nb, scan_ws + nb, total);
-  else
-    zk::tree_finish_scan_k<256, false><<<2, 256, 0, st>>>(
-        *t, n_dev, bump, publish, scan_ws, nb, scan_ws + nb, total);
+  zk::tree_finish_scan_k<256><<<2, 256, 0, st>>>(
+      *t, n_dev, bump, publish, scan_ws, nb, scan_ws + nb, total);
   ZK_LAUNCH_CHECK();
   return 0;
 }
@@ -2758,8 +2672,7 @@ int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
     zk::tree_serve_k<false><<<nb, zk::TR_T, 0, st>>>(
         *t, rx, *q, nullptr, nullptr, n_dev, ncap, r_op, r_xid, r_err, r_node, r_zxid,
         r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session, now_ms,
-        rank, pass, last, snap_base, snap_cap, &w.ctr[2], wslot, fired,
-        nullptr);
+        rank, pass, last, snap_base, snap_cap, &w.ctr[2], wslot, fired);
     ZK_LAUNCH_CHECK();
     // nodes freed by a pass are recycled from the next batch on: a reply of
     // this batch may still name them

@@ -149,8 +149,6 @@ struct ZkSessionTable {
 // ---- launchers (stream-ordered; return 0 or a hipError_t) ----------------
 int64_t zk_scan_workspace(int64_t n);
 int zk_scan_set_mode(int mode);
-// engine of the one-workgroup scans (ZKMI_SMALL_SCAN): 1 MFMA, 0 shuffle
-int zk_scan_small_mode(void);
 // the one-workgroup exclusive scan with an explicit engine (1 MFMA, 0 shfl)
 int zk_scan_small_i64_mode(const int64_t*, int64_t*, int64_t, int64_t*, int,
                            hipStream_t);
@@ -158,9 +156,9 @@ int zk_scan_excl_i64(const int64_t*, int64_t*, int64_t, int64_t*, int64_t*,
                      hipStream_t);
 int zk_scan_excl_i32(const int32_t*, int64_t*, int64_t, int64_t*, int64_t*,
                      hipStream_t);
-int zk_encode_requests2(const ZkReqBatch*, int64_t, int64_t*, int64_t*,
-                        int64_t*, int64_t*, uint8_t*, int64_t, int64_t*,
-                        int64_t, int32_t*, int32_t, hipStream_t);
+int zk_encode_requests(const ZkReqBatch*, int64_t, int64_t*, int64_t*,
+                       int64_t*, int64_t*, uint8_t*, int64_t, int64_t*,
+                       int64_t, int32_t*, int32_t, hipStream_t);
 int zk_encode_requests_presized(const ZkReqBatch*, int64_t, const int64_t*,
                                 const int64_t*, int64_t*, int64_t*, int64_t*,
                                 uint8_t*, int64_t, int64_t*, int64_t,
@@ -173,30 +171,26 @@ int zk_encode_connect_requests(const int32_t*, const int64_t*, const int32_t*,
                                const int64_t*, const int64_t*, const int32_t*,
                                const uint8_t*, int64_t, int64_t*, int64_t*,
                                int64_t*, int64_t*, uint8_t*, hipStream_t);
-int zk_encode_responses2(const ZkRespBatch*, const ZkNodeStore*,
-                         const int64_t*, int64_t, int64_t*, int64_t*,
-                         int64_t*, int64_t*, uint8_t*, int64_t, int32_t*,
-                         int32_t, int32_t, hipStream_t);
-int zk_encode_responses3(const ZkRespBatch*, const ZkNodeStore*,
-                         const int64_t*, int64_t, int64_t*, int64_t*, int64_t*,
-                         int64_t*, uint8_t*, int64_t, int32_t*, int32_t,
-                         int32_t, int64_t, hipStream_t);
+int zk_encode_responses(const ZkRespBatch*, const ZkNodeStore*,
+                        const int64_t*, int64_t, int64_t*, int64_t*,
+                        int64_t*, int64_t*, uint8_t*, int64_t, int32_t*,
+                        int32_t, int32_t, hipStream_t);
 int64_t zk_frame_scan_workspace(int64_t n);
-int zk_frame_scan5(const uint8_t*, const int64_t*, int64_t, int64_t,
-                   uint8_t*, int64_t, int64_t*, int32_t*, int64_t, int64_t*,
-                   int32_t, int32_t, int32_t, hipStream_t);
+int zk_frame_scan(const uint8_t*, const int64_t*, int64_t, int64_t,
+                  uint8_t*, int64_t, int64_t*, int32_t*, int64_t, int64_t*,
+                  int32_t, int32_t, int32_t, hipStream_t);
 int zk_frame_scan_stats(const uint8_t*, int64_t, int32_t, uint32_t*,
                         hipStream_t);
 int zk_frame_scan_dbg(int64_t* host, int64_t tiles);
 int zk_decode_replies(const uint8_t*, const int64_t*, const int32_t*,
                       const int64_t*, int64_t, const int64_t*, int64_t,
                       const ZkReplyOut*, hipStream_t);
-int zk_decode_replies_check2(const uint8_t*, const int64_t*, const int32_t*,
-                             const int64_t*, int64_t, const int64_t*, int64_t,
-                             const ZkReplyOut*, const int64_t*, const int32_t*,
-                             const int32_t*, unsigned long long*, int32_t,
-                             int64_t*, const uint8_t*, const int64_t*,
-                             hipStream_t);
+int zk_decode_replies_check(const uint8_t*, const int64_t*, const int32_t*,
+                            const int64_t*, int64_t, const int64_t*, int64_t,
+                            const ZkReplyOut*, const int64_t*, const int32_t*,
+                            const int32_t*, unsigned long long*, int32_t,
+                            int64_t*, const uint8_t*, const int64_t*,
+                            hipStream_t);
 int zk_expand_strings(const uint8_t*, const int64_t*, const int32_t*,
                       const int64_t*, int64_t, int64_t*, int32_t*,
                       hipStream_t);
@@ -221,24 +215,12 @@ int zk_tree_serve(const ZkTree*, const uint8_t*, const ZkReqOut*,
                   const int64_t*, int64_t, int32_t*, int32_t*, int32_t*,
                   int64_t*, int64_t*, int64_t*, int32_t*, int64_t*, int64_t*,
                   int64_t*, int64_t, int64_t, hipStream_t);
-int64_t zk_serve_tickets(int64_t);
+// (last int32: read_only; the finish is zk_tree_finish_scan's)
 int zk_tree_serve_frames(const ZkTree*, const uint8_t*, const int64_t*,
                          const int32_t*, const int64_t*, int64_t, int32_t*,
                          int32_t*, int32_t*, int64_t*, int64_t*, int64_t*,
                          int32_t*, int64_t*, int64_t*, int64_t*, int64_t,
-                         int64_t, int32_t, int64_t*, unsigned*,
-                         hipStream_t);
-int zk_tree_serve_frames2(const ZkTree*, const uint8_t*, const int64_t*,
-                          const int32_t*, const int64_t*, int64_t, int32_t*,
-                          int32_t*, int32_t*, int64_t*, int64_t*, int64_t*,
-                          int32_t*, int64_t*, int64_t*, int64_t*, int64_t,
-                          int64_t, int32_t, int64_t*, unsigned*, int32_t,
-                          hipStream_t);
-// zk_tree_serve_frames2's last flag word
-#define ZK_SERVE_FINISH 1
-#define ZK_SERVE_RO 2
-int zk_tree_finish(const ZkTree*, const int64_t*, int64_t, int32_t,
-                   hipStream_t);
+                         int64_t, int32_t, int64_t*, int32_t, hipStream_t);
 int zk_tree_finish_scan(const ZkTree*, const int64_t*, int64_t, int32_t,
                         int64_t, int64_t*, int64_t*, hipStream_t);
 int zk_tree_serve_ordered(const ZkTree*, const uint8_t*, const ZkReqOut*,
@@ -311,14 +293,10 @@ int zk_bench_check_notif(int64_t, int64_t, const uint64_t*, const int64_t*,
                          const int64_t*, const int32_t*, unsigned long long*,
                          hipStream_t);
 int64_t zk_route_workspace(int64_t n, int32_t world);
-int zk_route_requests(int64_t, int32_t, const int64_t*, const int32_t*,
-                      const uint8_t*, const int64_t*, const int32_t*,
-                      int32_t*, int64_t*, int32_t*, int64_t*, int32_t*,
-                      int64_t*, int64_t*, hipStream_t);
-int zk_route_requests2(int64_t, int32_t, int32_t, const int64_t*,
-                       const int32_t*, const uint8_t*, const int64_t*,
-                       const int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
-                       int32_t*, int64_t*, int64_t*, hipStream_t);
+int zk_route_requests(int64_t, int32_t, int32_t, const int64_t*,
+                      const int32_t*, const uint8_t*, const int64_t*,
+                      const int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
+                      int32_t*, int64_t*, int64_t*, hipStream_t);
 int zk_seg_pack(const uint8_t*, int64_t, const int64_t*, const int64_t*,
                 int64_t, const int64_t*, const int64_t*, int32_t, int32_t,
                 int64_t, uint8_t*, unsigned long long*, uint8_t*, int32_t,

@@ -241,9 +241,7 @@ ZkSessionTable session_table(const std::vector<Tensor>& v, int64_t span) {
 // -- ops ---------------------------------------------------------------------
 
 int64_t scan_workspace(int64_t n) { return zk_scan_workspace(n); }
-int64_t serve_tickets(int64_t ncap) { return zk_serve_tickets(ncap); }
 int64_t scan_set_mode(int64_t m) { return zk_scan_set_mode((int)m); }
-int64_t scan_small_mode() { return zk_scan_small_mode(); }
 
 // the one-workgroup scan (K10 / K13 block sums) on a chosen engine
 void scan_small(const Tensor& x, const Tensor& base, const Tensor& total,
@@ -280,7 +278,7 @@ void encode_requests(const std::vector<Tensor>& batch, int64_t n,
   const Tensor* r = &batch[0];
   const int64_t m = std::max<int64_t>(n, 1);
   int64_t* tab = Popt<int64_t>(xid_tab, I64, xid_mask + 1, "xid_tab", r);
-  hip_ok(zk_encode_requests2(
+  hip_ok(zk_encode_requests(
              &b, n, P<int64_t>(sizes, I64, m, "sizes", r),
              P<int64_t>(rec_off, I64, m, "rec_off", r),
              P<int64_t>(total, I64, 1, "total", r),
@@ -371,7 +369,7 @@ void encode_responses(const std::vector<Tensor>& resp,
                       int64_t ncap, const Tensor& sizes, const Tensor& rec_off,
                       const Tensor& total, const Tensor& ws, const Tensor& out,
                       const Tensor& err, bool presized, bool terminate,
-                      int64_t stage, bool prescanned) {
+                      bool prescanned) {
   TORCH_CHECK(!prescanned || presized,
               "zkmi: encode_responses prescanned needs presized");
   need(store, 4, "node store");
@@ -379,7 +377,7 @@ void encode_responses(const std::vector<Tensor>& resp,
   ZkRespBatch b = resp_batch(resp, slot, ncap, r);
   ZkNodeStore s = node_store(store, 0, r);
   const int64_t m = std::max<int64_t>(ncap, 1);
-  hip_ok(zk_encode_responses3(
+  hip_ok(zk_encode_responses(
              &b, &s, P<int64_t>(n_dev, I64, 1, "count", r), ncap,
              P<int64_t>(sizes, I64, m, "sizes", r),
              P<int64_t>(rec_off, I64, m, "rec_off", r),
@@ -388,7 +386,7 @@ void encode_responses(const std::vector<Tensor>& resp,
              P<uint8_t>(out, U8, 1, "out", r), out.numel(),
              P<int32_t>(err, I32, 1, "err", r),
              presized ? (prescanned ? 2 : 1) : 0,
-             terminate ? 1 : 0, stage, cur_stream()),
+             terminate ? 1 : 0, cur_stream()),
          "encode_responses");
 }
 
@@ -404,7 +402,7 @@ void frame_scan(const Tensor& buf, const c10::optional<Tensor>& n_dev,
   TORCH_CHECK(ws.numel() >= zk_frame_scan_workspace(n_cap),
               "zkmi: frame_scan workspace too small");
   const int64_t cap = foff.numel();
-  hip_ok(zk_frame_scan5(
+  hip_ok(zk_frame_scan(
              P<uint8_t>(buf, U8, 1, "buf"),
              Popt<int64_t>(n_dev, I64, 1, "n", &buf), n_cap, max_packet,
              P<uint8_t>(ws, U8, 1, "ws", &buf), ws.numel(),
@@ -470,7 +468,7 @@ void decode_replies_check(const Tensor& buf, const Tensor& foff,
   if (slot_off.has_value())
     TORCH_CHECK(slot_off->numel() >= data_len.numel(),
                 "zkmi: decode_replies_check: slot_off shorter than data_len");
-  hip_ok(zk_decode_replies_check2(
+  hip_ok(zk_decode_replies_check(
              P<uint8_t>(buf, U8, 1, "buf"),
              P<int64_t>(foff, I64, cap, "frame_off", &buf),
              P<int32_t>(flen, I32, cap, "frame_len", &buf),
@@ -575,7 +573,8 @@ void tree_free_compact(const std::vector<Tensor>& t, const Tensor& ws) {
          "tree_free_compact");
 }
 
-// tree_finish + the presized reply encode's block-sum scan in one launch
+// The serve's finish (after tree_serve_frames; zxid += *n_dev, or bump when
+// n_dev is None) + the presized reply encode's block-sum scan in one launch
 // (ws: the response workspace the serve wrote its block sums into; total:
 // the encode's total, then encode_responses(prescanned=True)).
 void tree_finish_scan(const std::vector<Tensor>& t,
@@ -631,14 +630,13 @@ void tree_serve(const std::vector<Tensor>& t, const Tensor& rx,
 }
 
 // tree_serve from K1's frame table: each lane parses its request frame in
-// registers (no K12 decode pass).
+// registers (no K12 decode pass).  No finish: tree_finish_scan follows.
 void tree_serve_frames(const std::vector<Tensor>& t, const Tensor& rx,
                        const Tensor& foff, const Tensor& flen,
                        const Tensor& n_dev, int64_t ncap,
                        const std::vector<Tensor>& r, int64_t session,
                        int64_t now_ms, int64_t wslot,
                        const c10::optional<Tensor>& fired,
-                       const c10::optional<Tensor>& tickets, bool finish,
                        const c10::optional<Tensor>& seqno, bool read_only) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
@@ -646,7 +644,7 @@ void tree_serve_frames(const std::vector<Tensor>& t, const Tensor& rx,
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
   TORCH_CHECK(wslot >= -1 && wslot < 64, "zkmi: watcher slot -1..63");
   const int64_t nb = (ncap + 255) / 256;
-  hip_ok(zk_tree_serve_frames2(
+  hip_ok(zk_tree_serve_frames(
              &s, P<uint8_t>(rx, U8, 1, "rx", d),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
@@ -662,21 +660,8 @@ void tree_serve_frames(const std::vector<Tensor>& t, const Tensor& rx,
              P<int64_t>(r[8], I64, ncap, "r.sizes", d),
              P<int64_t>(r[9], I64, nb, "r.block_sums", d), session, now_ms,
              (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
-             reinterpret_cast<unsigned*>(Popt<int32_t>(
-                 tickets, I32, zk_serve_tickets(ncap), "tickets", d)),
-             (finish ? ZK_SERVE_FINISH : 0) | (read_only ? ZK_SERVE_RO : 0),
-             cur_stream()),
+             read_only ? 1 : 0, cur_stream()),
          "tree_serve_frames");
-}
-
-// The serve's finish on its own (after tree_serve_frames(..., finish=False)):
-// zxid += *n_dev (or bump when n_dev is None).
-void tree_finish(const std::vector<Tensor>& t, const c10::optional<Tensor>& n_dev,
-                 int64_t bump, bool publish) {
-  ZkTree s = tree(t);
-  hip_ok(zk_tree_finish(&s, Popt<int64_t>(n_dev, I64, 1, "count", &t[0]), bump,
-                        publish ? 1 : 0, cur_stream()),
-         "tree_finish");
 }
 
 int64_t tree_order_workspace(int64_t n) {
@@ -1049,7 +1034,7 @@ void route_requests(int64_t n, int64_t world, const Tensor& poff,
   TORCH_CHECK(world >= 1 && world <= 64, "zkmi: route world 1..64");
   TORCH_CHECK(self >= 0 && self < world, "zkmi: route self rank");
   const Tensor* r = &poff;
-  hip_ok(zk_route_requests2(
+  hip_ok(zk_route_requests(
              n, (int32_t)world, (int32_t)self,
              P<int64_t>(poff, I64, n, "path_off"),
              P<int32_t>(plen, I32, n, "path_len", r),
@@ -1174,7 +1159,6 @@ void session_install(const std::vector<Tensor>& tab, const Tensor& rec,
 TORCH_LIBRARY(zkmi, m) {
   m.def("scan_workspace(int n) -> int", &scan_workspace);
   m.def("scan_set_mode(int mode) -> int", &scan_set_mode);
-  m.def("scan_small_mode() -> int", &scan_small_mode);
   m.def("scan_small(Tensor x, Tensor(a!) base, Tensor(b!) total, "
         "bool mfma) -> ()", &scan_small);
   m.def("scan_excl(Tensor x, Tensor(a!) base, Tensor(b!) total, "
@@ -1198,8 +1182,7 @@ TORCH_LIBRARY(zkmi, m) {
   m.def("encode_responses(Tensor[] resp, Tensor? slot, Tensor[] store, "
         "Tensor count, int ncap, Tensor(a!) sizes, Tensor(b!) rec_off, "
         "Tensor(c!) total, Tensor(d!) ws, Tensor(e!) out, Tensor(f!) err, "
-        "bool presized, bool terminate, int stage=0, "
-        "bool prescanned=False) -> ()",
+        "bool presized, bool terminate, bool prescanned=False) -> ()",
         &encode_responses);
   m.def("frame_scan_workspace(int n) -> int", &frame_scan_workspace);
   m.def("frame_scan(Tensor buf, Tensor? n, int n_cap, int max_packet, "
@@ -1247,10 +1230,8 @@ TORCH_LIBRARY(zkmi, m) {
   m.def("tree_serve_frames(Tensor(a!)[] tree, Tensor rx, Tensor frame_off, "
         "Tensor frame_len, Tensor count, int ncap, Tensor(b!)[] out, "
         "int session, int now_ms, int wslot=-1, Tensor(c!)? fired=None, "
-        "Tensor(d!)? tickets=None, bool finish=True, Tensor? seqno=None, "
-        "bool read_only=False) -> ()", &tree_serve_frames);
-  m.def("tree_finish(Tensor(a!)[] tree, Tensor? count, int bump=0, "
-        "bool publish=True) -> ()", &tree_finish);
+        "Tensor? seqno=None, bool read_only=False) -> ()",
+        &tree_serve_frames);
   m.def("tree_order_workspace(int n) -> int", &tree_order_workspace);
   m.def("tree_order_stats_offset(int n) -> int", &tree_order_stats_offset);
   m.def("tree_serve_ordered(Tensor(a!)[] tree, Tensor rx, Tensor[] requests, "
@@ -1304,7 +1285,6 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor path_arena, Tensor rx, Tensor[] reply, Tensor(a!) acc, "
         "Tensor? want=None) -> ()", &bench_check_notif);
   m.def("route_workspace(int n, int world) -> int", &route_workspace);
-  m.def("serve_tickets(int ncap) -> int", &serve_tickets);
   m.def("route_requests(int n, int world, Tensor path_off, Tensor path_len, "
         "Tensor arena, Tensor idx, Tensor xid, Tensor(a!) owner, "
         "Tensor(b!) idx_s, Tensor(c!) xid_s, Tensor(d!) path_off_s, "

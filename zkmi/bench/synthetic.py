@@ -22,7 +22,6 @@ sync-free and no byte past a stream's end is walked.
 version CAS and ACL encode (BASELINE config 3).
 """
 
-import os
 import time
 
 import numpy as np
@@ -34,52 +33,17 @@ from ..ops import batch as B
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 
-# ZKMI_SERVE_TICKETS=1: the serve launch's last workgroup does the tree
-# finish (sign-off tickets) instead of a tree_finish_k launch.  Off by
-# default: every workgroup's release fence costs an L2 writeback on a
-# multi-XCD part — tree_serve 90 -> 231 us, the GET step 0.651 -> 0.718 ms
-# (profiles/r5_regression_ab.md); the extra launch is far cheaper.
-_SERVE_TICKETS = os.environ.get('ZKMI_SERVE_TICKETS', '0') == '1'
-# ZKMI_GET_STAGE: the LDS bytes per workgroup the GET pipelines' reply
-# encode asks for (0: the encoder's 28 KiB).  Uniform GET replies need only
-# the writer's 7 KiB header table, but 8 KiB measured no faster for them
-# (0.581 vs 0.581 ms) and slowed variable payloads, whose replies go
-# through the LDS image (uniform 0-200 B 0.710 -> 0.972 ms,
-# profiles/r5_get_stage_ab.log): off.
-_GET_STAGE = int(os.environ.get('ZKMI_GET_STAGE', '0'))
-# ZKMI_SERVE_RO=0: the GET pipelines serve with the general serve kernel
-# instead of its read-only instance
-_SERVE_RO = os.environ.get('ZKMI_SERVE_RO', '1') == '1'
-# ZKMI_FREE_COMPACT=0: no free-ring compaction after write batches (trees
-# built with compact_free=True; GpuTree.free_compact)
-_FREE_COMPACT = os.environ.get('ZKMI_FREE_COMPACT', '1') == '1'
-# ZKMI_FINISH_SCAN=0: the tree finish and the reply encode's block-sum scan
-# as two launches again (tree_finish_scan_k runs them as one)
-_FINISH_SCAN = os.environ.get('ZKMI_FINISH_SCAN', '1') == '1'
 # the largest batch tree_seq_order numbers
 _SEQ_MAX = 1 << 24
-# ZKMI_GET_PRESIZED=0: the GET pipelines' request encode runs its own sizes
-# pass instead of taking the generator's (bench_gen_get sizes / bsum)
-_GET_PRESIZED = os.environ.get('ZKMI_GET_PRESIZED', '1') == '1'
-# ZKMI_STORM_STREAMS=1: the one-member storm step on one stream (its
-# handshake and expiry no longer beside the encode / the reply decode)
-_STORM_STREAMS = os.environ.get('ZKMI_STORM_STREAMS', '2') != '1'
-# ZKMI_SRV_GROUP: K1 tiles a wave on the GPU server's request streams, for
-# every workload (unset: the defaults below).  Request streams of equal-
-# sized frames without length-like words take groups (the groups' walk
-# steps over a run of equal frames): GET 4 tiles a wave (0.5255 vs 0.5337
-# ms a step at 1), the storm's identical creates 8 (1.298 vs 1.316 at 4,
-# 1.344 at 1; profiles/r6_srv_group_ab.log,
-# r6_srv_group_storm_mix_ab.log).  The others stay at one: SET_DATA
-# versions read as frame lengths make phantom chains, which the per-tile
-# maps settle and a group's walked tiles do not (the watch workload's
-# version-84 step took 32.6 ms against a 2.4 ms median at 4 tiles a wave,
-# tests/test_watch_sustained.py; mix gained 1.2 % at 4).
-_SRV_GROUP_ENV = (int(os.environ['ZKMI_SRV_GROUP'])
-                  if os.environ.get('ZKMI_SRV_GROUP') else None)
-_SRV_GROUP = _SRV_GROUP_ENV
-_GET_SRV_GROUP = _SRV_GROUP_ENV or 4
-_STORM_SRV_GROUP = _SRV_GROUP_ENV or 8
+# K1 tiles a wave on the GPU server's request streams.  Request streams of
+# equal-sized frames without length-like words take groups (the groups' walk
+# steps over a run of equal frames): GET 4 tiles a wave, the storm's
+# identical creates 8.  The others stay at one: SET_DATA versions read as
+# frame lengths make phantom chains, which the per-tile maps settle and a
+# group's walked tiles do not (README, "Measured and rejected").
+_SRV_GROUP = 1
+_GET_SRV_GROUP = 4
+_STORM_SRV_GROUP = 8
 
 
 def _len(total):
@@ -250,8 +214,8 @@ class GpuTree(object):
         self.dirty_list = torch.empty(cap, dtype=I64, device=dev)
         self.hcap = hcap
         # write workloads: the free ring's pending entries re-sorted after
-        # every served batch (free_compact; ZKMI_FREE_COMPACT=0 turns it off)
-        self.compact_free = compact_free and _FREE_COMPACT
+        # every served batch (free_compact)
+        self.compact_free = compact_free
         self.free_ws = None
         # the tree / node-store descriptor lists torch.ops.zkmi takes
         # (csrc/torch/zkmi_ops.cpp tree() / node_store() field order)
@@ -446,12 +410,7 @@ class GpuServer(object):
         self.scanner = B.FrameScanner(cap_frames, dev, window=window,
                                       group=group)
         self.ows = None                   # ordered-serve workspace (lazy)
-        self.enc_stage = 0                # K13 LDS per workgroup (0: default)
         self.total_err = B._total_err(dev)  # the reply encode's scalars
-        # the serve launch's sign-off counters (its last workgroup does the
-        # tree's finish: no separate launch); this server's own, zero
-        self.tickets = torch.zeros(_lib.lib().serve_tickets(cap_frames),
-                                   dtype=I32, device=dev)
         self.notif = None
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
@@ -572,7 +531,6 @@ class GpuServer(object):
         out = [r.opcode, r.xid, r.err, r.node, r.zxid, r.path_off,
                r.path_len, r.slot, self.presized[0], self.presized[1]]
         now = int(time.time() * 1000)
-        fuse = False
         seqno = self._seq_order(rx, ft) if self.seq_order else None
         if ordered:
             if self.ows is None:
@@ -585,23 +543,18 @@ class GpuServer(object):
                                  wslot, self.fired if self.tree.watch
                                  is not None else None, seqno)
         else:
-            fuse = _FINISH_SCAN and not _SERVE_TICKETS
             L.tree_serve_frames(self.tree.tensors, rx, ft.off, ft.length,
                                 ft.count, self.cap_frames, out, session, now,
                                 wslot, self.fired if self.tree.watch
-                                is not None else None,
-                                self.tickets if _SERVE_TICKETS else None,
-                                not fuse, seqno, self.read_only)
-            if fuse:
-                # the finish and K13's block-sum scan: one launch
-                L.tree_finish_scan(self.tree.tensors, ft.count, 0, True,
-                                   self.cap_frames, self.presized[1],
-                                   self.total_err[0])
+                                is not None else None, seqno, self.read_only)
+            # the finish and K13's block-sum scan: one launch
+            L.tree_finish_scan(self.tree.tensors, ft.count, 0, True,
+                               self.cap_frames, self.presized[1],
+                               self.total_err[0])
         out, rec_off, total, err = B.encode_responses(
             r, self.tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
-            stage=self.enc_stage, total_err=self.total_err,
-            prescanned=fuse)
+            total_err=self.total_err, prescanned=not ordered)
         if self.tree.compact_free:
             self.tree.free_compact()
         self.last_rec_off = rec_off         # reply frame starts (R2 splits)
@@ -745,8 +698,7 @@ class GetPipeline(object):
         self.server = GpuServer(tree, n, n * (4 + 16 + 4 + dmax + 68) + 64,
                                 window=B.frame_window(17 + maxpath),
                                 seq_order=False, group=_GET_SRV_GROUP)
-        self.server.read_only = _SERVE_RO
-        self.server.enc_stage = _GET_STAGE
+        self.server.read_only = True
         self.rwindow = B.frame_window(4 + 16 + 4 + dmax + 68)
         lo, hi = tree.data_dist or (tree.data_bytes, tree.data_bytes)
         self.rscanner = B.FrameScanner(n, dev, window=self.rwindow,
@@ -762,10 +714,8 @@ class GetPipeline(object):
         self.poff = torch.empty(n, dtype=I64, device=dev)
         self.plen = torch.empty(n, dtype=I32, device=dev)
         # the encode's sizes pass, written by the generator
-        self.sizes = torch.empty(n, dtype=I64, device=dev) \
-            if _GET_PRESIZED else None
-        self.bsum = torch.empty((n + 255) // 256, dtype=I64, device=dev) \
-            if _GET_PRESIZED else None
+        self.sizes = torch.empty(n, dtype=I64, device=dev)
+        self.bsum = torch.empty((n + 255) // 256, dtype=I64, device=dev)
         self.gstate = None      # device {seed, step} (see capture)
 
     def _device_seed(self):
@@ -867,8 +817,7 @@ class GetPipeline(object):
                             self.acl_len, self.acl_arena)
         tx, rec_off, total, err = B.encode_requests(
             rb, self.xt, out=self.tx,
-            presized=(self.sizes, self.bsum) if self.sizes is not None
-            else None)
+            presized=(self.sizes, self.bsum))
         yield
         srv = self.server.serve_steps(tx, _len(total))
         next(srv)
@@ -1647,9 +1596,8 @@ class StormPipeline(object):
         self.chk = torch.zeros(1, dtype=I64, device=dev)
         self.hs_ok = torch.ones(1, dtype=torch.bool, device=dev)
         # one member: the handshake beside the request encode, the expiry
-        # beside the reply decode, on this second stream (ZKMI_STORM_STREAMS=1:
-        # everything on the caller's)
-        self.side = torch.cuda.Stream(dev) if _STORM_STREAMS else None
+        # beside the reply decode, on this second stream
+        self.side = torch.cuda.Stream(dev)
         self.cr_tx = torch.empty(256, dtype=U8, device=dev)
         self.cr_ws = torch.empty(_lib.lib().scan_workspace(2),
                                  dtype=I64, device=dev)
@@ -1825,26 +1773,22 @@ class StormPipeline(object):
         # ensemble passes host ids, see _replicated_run)
         sess_dev = t.counters[_lib.TC_SESS:_lib.TC_SESS + 1]
         torch.add(self.kdev, self.sid0, out=sess_dev)
-        if self.world > 1:
-            torch.add(self.sid_base, self.kdev + 1, out=self.sess_tab)
-        if self.world == 1 and self.side is not None:
+        if self.world == 1:
             return self._step_two_streams(resume, sess_dev, validate, acc)
+        torch.add(self.sid_base, self.kdev + 1, out=self.sess_tab)
         o, bound, outcome, resp = self._handshake(resume)
         self._check_handshake(resume, sess_dev, o, bound, outcome, resp)
         rb = self._batch()
-        if self.world > 1:
-            rep = self._replicated_run(rb, resume)
-        else:
-            rep, _ = self.drv.run(rb, session=_lib.SESS_DEV)
+        rep = self._replicated_run(rb, resume)
         self.last = (rb, rep)
-        if not resume and self.world > 1:
+        if not resume:
             # the new session's first batch: the created paths (offsets into
             # the reply stream kept with them), for cross_read
             self.first = (self.my_rx.clone(), rep.pay_off[:n].clone(),
                           rep.pay_len[:n].clone())
         self._check_replies(rb, rep)
         expire_ok = True
-        if not resume and self.k >= 1 and self.world > 1:
+        if not resume and self.k >= 1:
             # the generation before expires on every member, which holds
             # all members' sessions' nodes (the replicated tree): each of
             # them created two batches — here its first batch (our
@@ -1857,9 +1801,6 @@ class StormPipeline(object):
                 t.expire(_lib.SESS_DEV, self.removed)
             self.sessions.close(self.prev_recs[:, 0].contiguous())
             expire_ok = self.removed[0] == 2 * n * self.world
-        elif not resume and self.k >= 1:
-            self._expire_prev(sess_dev)
-            expire_ok = self.removed[0] == 2 * n
         return self._tally(validate, acc, expire_ok)
 
     def _check_handshake(self, resume, sess_dev, o, bound, outcome, resp):

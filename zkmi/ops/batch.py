@@ -13,7 +13,6 @@ K10 :func:`encode_requests`; K11 :func:`encode_set_watches`; K12
 :func:`decode_requests`; K13 :func:`encode_responses`.
 """
 
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -29,11 +28,9 @@ I64 = torch.int64
 I32 = torch.int32
 U8 = torch.uint8
 
+# K1 tiles a wave takes on streams of large frames (FrameScanner group)
+_FS_GROUP = 8
 
-
-# K1 tiles a wave takes on streams of large frames (FrameScanner group;
-# ZKMI_FS_GROUP: 1, 2, 4, 8 or 16)
-_FS_GROUP = int(os.environ.get('ZKMI_FS_GROUP', '8'))
 
 def _dev(device):
     return torch.device(device) if device is not None else \
@@ -679,15 +676,13 @@ def response_workspace(cap, device):
 
 
 def encode_responses(resp, store, out_cap, out=None, stream=None,
-                     presized=None, terminate=False, stage=0,
-                     total_err=None, prescanned=False):
+                     presized=None, terminate=False, total_err=None,
+                     prescanned=False):
     """K13: server-mode reply encode -> (bytes, rec_off, total, err).
     ``store``: the node store's tensors [slab, slot_off, data_len,
     slot_cap] (:attr:`zkmi.bench.synthetic.GpuTree.store`).
     ``presized``: the (sizes, workspace) pair of :func:`response_workspace`
     already filled by the producer; the sizes pass is then skipped.
-    ``stage``: LDS bytes per workgroup (0: the encoder's default; uniform
-    GET_DATA replies need only 8 KiB, more workgroups then fit a CU).
     ``total_err``: the (total, err) pair to write (default: new ones);
     ``prescanned``: the presized workspace's block bases and ``total`` were
     already computed (the tree's finish_scan launch)."""
@@ -707,7 +702,7 @@ def encode_responses(resp, store, out_cap, out=None, stream=None,
         L.encode_responses(resp.tensors(), resp.slot, list(store), resp.count,
                            cap, sizes, rec_off, total, ws, out, err,
                            presized is not None, bool(terminate),
-                           int(stage), bool(prescanned))
+                           bool(prescanned))
     return out, rec_off, total, err
 
 
