@@ -3,7 +3,8 @@
 # gpurun on this pool).
 PY ?= python
 
-.PHONY: all build test test-gpu check lint sanitize bench bench-full \
+.PHONY: all build test test-gpu check lint sanitize sanitize-parse bench \
+	bench-full \
 	bench-all prof clean
 
 all: build
@@ -17,13 +18,16 @@ test:                     ## CPU suite (fake ZooKeeper, gloo, host codec)
 test-gpu:                 ## kernel numerics + GPU pipelines (needs a GPU)
 	$(PY) -m pytest tests -x -q -m gpu
 
-check: lint sanitize      ## style + sanitizer runs
+check: lint sanitize sanitize-parse   ## style + sanitizer runs
 
 lint:
 	$(PY) tools/lint.py
 
 sanitize:                 ## host codec suites under ASan + UBSan
 	bash tools/sanitize_host.sh
+
+sanitize-parse:           ## the device request parser, host build, ASan + UBSan
+	bash tools/sanitize_parse.sh
 
 bench:                    ## headline benchmark, 1 GPU (timed steps only)
 	$(PY) bench.py

@@ -199,11 +199,19 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
         const int32_t cnt = max(ld_be32(b), 0);
         const int64_t k = skip_strings(b + 4, A - 4, cnt);
         if (k < 0) { status = ST_BAD_DECODE; break; }
+        // a rejected row points at nothing (pay_off -1, pay_len / aux 0):
+        // the short-Stat test comes before the payload fields are set.  A
+        // GET_CHILDREN2 reply with good names and a short Stat used to keep
+        // pay_off / pay_len / aux0 = count, and a consumer expanding by
+        // aux0 listed the children of a rejected reply.
+        if (op == OP_GET_CHILDREN2 && 4 + k + STAT_BYTES > A) {
+          status = ST_BAD_DECODE;
+          break;
+        }
         poff = foff[i] + 20;
         plen = (int32_t)k;
         a0 = cnt;
         if (op == OP_GET_CHILDREN2) {
-          if (4 + k + STAT_BYTES > A) { status = ST_BAD_DECODE; break; }
           if (tail_ok && 4 + k + STAT_BYTES == A) read_stat_regs(sw, o, i);
           else read_stat(b + 4 + k, o, i);
         }
@@ -223,11 +231,11 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
       }
       case OP_NOTIFICATION: {
         if (A < 12) { status = ST_BAD_DECODE; break; }
-        a0 = ld_be32(b);
-        a1 = ld_be32(b + 4);
         int32_t l = ld_be32(b + 8);
         if (l < 0) l = 0;
         if (12 + (int64_t)l > A) { status = ST_BAD_DECODE; break; }
+        a0 = ld_be32(b);                  // (type / state: accepted rows only)
+        a1 = ld_be32(b + 4);
         poff = foff[i] + 28;
         plen = l;
         break;

@@ -1523,7 +1523,9 @@ ZK_DEV int32_t seq_parent(const uint8_t* rx, int64_t off, int32_t len,
   uint32_t h[3];
   __builtin_memcpy(h, b, 12);
   const int32_t pl = (int32_t)bswap32(h[2]);
-  if ((int32_t)bswap32(h[1]) != OP_CREATE || pl < 2 || 12 + pl + 12 > len)
+  // (64-bit: a path length word near 2^31 overflowed `12 + pl + 12` as int
+  // and passed, and the '/' search then read 2 GiB past the frame)
+  if ((int32_t)bswap32(h[1]) != OP_CREATE || pl < 2 || (int64_t)pl + 24 > len)
     return 0;
   if (!(ld_be32(b + len - 4) & CF_SEQUENTIAL)) return 0;
   *p = b + 12;
@@ -1557,7 +1559,7 @@ ZK_DEV uint64_t seq_key(const uint8_t* rx, int64_t off, int32_t len) {
                "v"(W[10]), "v"(W[11]), "v"(W[12]), "v"(W[13]), "v"(W[14]),
                "v"(W[15]), "v"(fl));
   const int32_t pl = (int32_t)bswap32(W[2]);
-  if ((int32_t)bswap32(W[1]) != OP_CREATE || pl < 2 || 12 + pl + 12 > len ||
+  if ((int32_t)bswap32(W[1]) != OP_CREATE || pl < 2 || (int64_t)pl + 24 > len ||
       !(bswap32(fl) & CF_SEQUENTIAL))
     return 0;
   if (pl > 52) {

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "zk_abi.h"
+#include "zk_wire.h"   // opcodes, ST_* / ERR_*, bswap32/64, ld_be32/64
 
 #define ZK_DEV __device__ __forceinline__
 
@@ -21,40 +22,11 @@ enum : int32_t { SC_NEW = 0, SC_RESUMED = 1, SC_EXPIRED = 2, SC_REFUSED = 3,
 
 constexpr int WAVE = 64;
 
-// opcodes (lib/zk-consts.js:84-105; csrc/proto mirror, tests check parity)
-enum : int32_t {
-  OP_NOTIFICATION = 0, OP_CREATE = 1, OP_DELETE = 2, OP_EXISTS = 3,
-  OP_GET_DATA = 4, OP_SET_DATA = 5, OP_GET_ACL = 6, OP_SET_ACL = 7,
-  OP_GET_CHILDREN = 8, OP_SYNC = 9, OP_PING = 11, OP_GET_CHILDREN2 = 12,
-  OP_CHECK = 13, OP_MULTI = 14, OP_AUTH = 100, OP_SET_WATCHES = 101,
-  OP_SASL = 102, OP_CREATE_SESSION = -10, OP_CLOSE_SESSION = -11,
-  OP_ERROR = -1, OP_UNKNOWN = -1000
-};
-enum : int32_t {
-  XID_NOTIFICATION = -1, XID_PING = -2, XID_AUTH = -4, XID_SET_WATCHES = -8
-};
-enum : int32_t { ERR_OK = 0, ERR_SYSTEM = -1, ERR_UNIMPLEMENTED = -6,
-                 ERR_BAD_ARGUMENTS = -8, ERR_NO_NODE = -101,
-                 ERR_BAD_VERSION = -103, ERR_NO_CHILDREN_FOR_EPHEMERALS = -108,
-                 ERR_NODE_EXISTS = -110, ERR_NOT_EMPTY = -111,
-                 ERR_INVALID_ACL = -114 };
 // CREATE flags (lib/zk-buffer.js createFlags mapping)
 enum : int32_t { CF_EPHEMERAL = 1, CF_SEQUENTIAL = 2 };
-// per-record decode status
-enum : int32_t { ST_OK = 0, ST_BAD_DECODE = 1, ST_NO_XID = 2,
-                 ST_BAD_OPCODE = 3 };
 constexpr int32_t STAT_BYTES = 68;
 constexpr int64_t MAX_PACKET = 16 * 1024 * 1024;
 
-ZK_DEV uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-ZK_DEV uint64_t bswap64(uint64_t v) { return __builtin_bswap64(v); }
-
-ZK_DEV int32_t ld_be32(const uint8_t* p) {
-  uint32_t v; __builtin_memcpy(&v, p, 4); return (int32_t)bswap32(v);
-}
-ZK_DEV int64_t ld_be64(const uint8_t* p) {
-  uint64_t v; __builtin_memcpy(&v, p, 8); return (int64_t)bswap64(v);
-}
 ZK_DEV void st_be32(uint8_t* p, int32_t x) {
   uint32_t v = bswap32((uint32_t)x); __builtin_memcpy(p, &v, 4);
 }

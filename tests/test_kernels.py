@@ -1,6 +1,9 @@
 """Numerics of the HIP batch codec (K1-K13) against the pure-Python Jute
 oracle (zkmi/jute.py), which itself is pinned to the reference's golden
-vectors in test_proto.py.  All tests here need an MI355X."""
+vectors in test_proto.py.  The decode tests here (K2-K9, K12) feed the
+kernels frames the oracle encoded itself: the accept side.  Their reject
+side — malformed, cut and over-long frames, unknown xids and opcodes — is
+in tests/test_gpu_decode_malformed.py.  All tests here need an MI355X."""
 
 import os
 

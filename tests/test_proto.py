@@ -208,11 +208,12 @@ def test_consts_tables():
 
 
 def test_kernel_opcode_table_matches():
-    """csrc/kernels/zk_common.h mirrors the opcode/xid constants."""
+    """csrc/kernels/zk_wire.h (included by zk_common.h) mirrors the
+    opcode/xid constants."""
     import os
     import re
     src = open(os.path.join(os.path.dirname(__file__), '..', 'csrc',
-                            'kernels', 'zk_common.h')).read()
+                            'kernels', 'zk_wire.h')).read()
     for name, val in consts.OP_CODES.items():
         m = re.search(r'OP_%s = (-?\d+)' % name, src)
         assert m is not None and int(m.group(1)) == val, name

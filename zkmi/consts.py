@@ -2,7 +2,7 @@
 
 Parity: ``lib/zk-consts.js:13-138`` of the reference (perm masks, create flags,
 error codes + text, opcodes, notification types, keeper states, special xids).
-The same numbers are mirrored for native code in ``csrc/kernels/zk_common.h``
+The same numbers are mirrored for native code in ``csrc/kernels/zk_wire.h``
 (HIP kernels) and ``csrc/host/zk_host_codec.cpp``; ``tests/test_proto.py``
 checks the tables agree.
 """
