@@ -47,7 +47,7 @@ __global__ __launch_bounds__(BG_T) void bench_gen_get(
     const int64_t v = leaf0 + (int64_t)(((r >> 32) * (uint64_t)nleaves) >> 32);
     idx[i] = v;
     xid[i] = (int32_t)(((uint32_t)xid_base + (uint32_t)i) & 0x7fffffffu);
-    const int64_t pw = node_pw[v];         // offset << 24 | length (tree.hip)
+    const int64_t pw = node_pw[v];         // offset << 24 | length (zk_tree.h)
     const int32_t pl = (int32_t)(pw & 0xFFFFFF);
     path_off[i] = pw >> 24;
     path_len[i] = pl;

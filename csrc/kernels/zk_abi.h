@@ -98,7 +98,18 @@ struct ZkReqOut {
   int64_t cap;
 };
 
-// The GPU-resident synthetic server's tree (tree.hip).
+// tree_serve_k's reply descriptors for K13 (ncap rows; block_sums:
+// ceil(ncap / 256)).  slot may be null; sizes and block_sums may be null,
+// both or neither.
+struct ZkServeOut {
+  int32_t *opcode, *xid, *err;
+  int64_t *node, *zxid, *path_off;
+  int32_t* path_len;
+  int64_t *slot, *sizes, *block_sums;
+};
+
+// The GPU-resident synthetic server's tree (zk_tree.h; kernels in tree.hip
+// and tree_{order,seq,list,watch}.hip).
 struct ZkTree {
   int64_t* ht;                 // [2 * (mask + 1)] interleaved {key, val}
   int64_t mask;
@@ -212,23 +223,19 @@ int zk_tree_ht_reset(const ZkTree*, hipStream_t);
 int64_t zk_tree_free_workspace(int64_t cap);
 int zk_tree_free_compact(const ZkTree*, int64_t*, hipStream_t);
 int zk_tree_serve(const ZkTree*, const uint8_t*, const ZkReqOut*,
-                  const int64_t*, int64_t, int32_t*, int32_t*, int32_t*,
-                  int64_t*, int64_t*, int64_t*, int32_t*, int64_t*, int64_t*,
-                  int64_t*, int64_t, int64_t, hipStream_t);
+                  const int64_t*, int64_t, const ZkServeOut*, int64_t,
+                  int64_t, hipStream_t);
 // (last int32: read_only; the finish is zk_tree_finish_scan's)
 int zk_tree_serve_frames(const ZkTree*, const uint8_t*, const int64_t*,
-                         const int32_t*, const int64_t*, int64_t, int32_t*,
-                         int32_t*, int32_t*, int64_t*, int64_t*, int64_t*,
-                         int32_t*, int64_t*, int64_t*, int64_t*, int64_t,
-                         int64_t, int32_t, int64_t*, int32_t, hipStream_t);
+                         const int32_t*, const int64_t*, int64_t,
+                         const ZkServeOut*, int64_t, int64_t, int32_t,
+                         int64_t*, int32_t, hipStream_t);
 int zk_tree_finish_scan(const ZkTree*, const int64_t*, int64_t, int32_t,
                         int64_t, int64_t*, int64_t*, hipStream_t);
 int zk_tree_serve_ordered(const ZkTree*, const uint8_t*, const ZkReqOut*,
-                          const int64_t*, int64_t, int32_t*, int32_t*,
-                          int32_t*, int64_t*, int64_t*, int64_t*, int32_t*,
-                          int64_t*, int64_t*, int64_t*, int64_t, int64_t,
-                          uint8_t*, int64_t, int32_t, int64_t, int64_t,
-                          int32_t, int64_t*, hipStream_t);
+                          const int64_t*, int64_t, const ZkServeOut*, int64_t,
+                          int64_t, uint8_t*, int64_t, int32_t, int64_t,
+                          int64_t, int32_t, int64_t*, hipStream_t);
 int zk_watch_events(const int32_t*, const int32_t*, const int64_t*, int64_t,
                     const int64_t*, int64_t*, int64_t, int32_t*, int32_t*,
                     int64_t*, int32_t*, int64_t*, hipStream_t);
@@ -240,7 +247,7 @@ int64_t zk_tree_order_workspace(int64_t);
 int64_t zk_tree_order_stats_offset(int64_t);
 int zk_tree_expire(const ZkTree*, int64_t, int64_t, unsigned long long*,
                    hipStream_t);
-// SEQUENTIAL numbers of a batch in stream order (tree.hip seq_*): bytes of
+// SEQUENTIAL numbers of a batch in stream order (tree_seq.hip): bytes of
 // the workspace for ncap requests, the prefix of it that must be zero when
 // it is first used (the kernels leave it zero), and the ordering itself
 // (writes seqno[ncap]; bumps each parent's cversion once per batch).
@@ -258,7 +265,7 @@ int zk_tree_seq_order(const ZkTree*, const uint8_t*, const int64_t*,
 // data), out[1] = live nodes, out[2] = hash entries in use (live +
 // tombstones), out[3] = tombstones
 int zk_tree_digest(const ZkTree*, unsigned long long*, hipStream_t);
-// GET_CHILDREN / GET_CHILDREN2 batches from the tree (tree.hip list_*):
+// GET_CHILDREN / GET_CHILDREN2 batches from the tree (tree_list.hip):
 // bytes of the workspace for ncap requests, and the serve itself (frames,
 // count, ncap, watcher slot, max reply frame, want[node cap] int32 idling at
 // 0x7fffffff, workspace + bytes, out + capacity, rec_off[ncap], total, err,
@@ -323,6 +330,7 @@ static_assert(sizeof(ZkNodeStore) == 5 * 8, "ZkNodeStore layout");
 static_assert(sizeof(ZkRespBatch) == 10 * 8, "ZkRespBatch layout");
 static_assert(sizeof(ZkReplyOut) == 12 * 8, "ZkReplyOut layout");
 static_assert(sizeof(ZkReqOut) == 12 * 8, "ZkReqOut layout");
+static_assert(sizeof(ZkServeOut) == 10 * 8, "ZkServeOut layout");
 static_assert(sizeof(ZkSessionTable) == 7 * 8, "ZkSessionTable layout");
 static_assert(sizeof(ZkTree) == 27 * 8, "ZkTree layout");
 static_assert(offsetof(ZkTree, store) == 9 * 8, "ZkTree.store");

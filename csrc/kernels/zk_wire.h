@@ -1,8 +1,10 @@
 // Jute wire constants and the server-mode request parse (K12) in plain C++:
 // no HIP include, so the host compiler builds the very text the kernels run
 // (tools/fuzz_reqparse.cpp puts it under ASan + UBSan on a machine without
-// a GPU).  zk_common.h / zk_reqparse.h include this header; under hipcc
-// every function here is a __host__ __device__ inline, elsewhere an inline.
+// a GPU).  zk_common.h includes this header; under hipcc every function
+// here is a __host__ __device__ inline, elsewhere an inline.  parse_request
+// is shared by decode_requests_k (SoA output) and the GPU server's fused
+// serve (tree.hip tree_serve_k), which parses each frame in registers.
 // Reference: lib/zk-consts.js:84-105 (opcodes), lib/zk-buffer.js:58-253
 // (request layouts).
 #pragma once

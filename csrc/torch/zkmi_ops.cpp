@@ -7,7 +7,7 @@
 // on a launch error.  The kernels' launchers are the extern "C" functions
 // of libzkmi_hip.so; the batch descriptors they take (ZkReqBatch, ZkTree,
 // ...) are assembled here from tensor lists in the field order of
-// csrc/kernels/zk_batch.h and tree.hip.  Mutated arguments are marked
+// csrc/kernels/zk_abi.h.  Mutated arguments are marked
 // (a!) in the schemas.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -115,7 +115,7 @@ ZkTree tree(const std::vector<Tensor>& v) {
               v.size());
   const Tensor* r = &v[0];
   ZkTree t;
-  // 64-byte entries: key, val, lengths, the path's head (tree.hip HT_W)
+  // 64-byte entries: key, val, lengths, the path's head (zk_tree.h HT_W)
   const int64_t hw = v[0].numel() / 8;
   TORCH_CHECK(hw > 0 && (hw & (hw - 1)) == 0 && v[0].numel() % 8 == 0,
               "zkmi: tree.ht must hold a power of two of 8-word entries");
@@ -199,6 +199,25 @@ ZkReqOut req_out(const std::vector<Tensor>& v, int64_t cap, const Tensor* r) {
   o.vec_count = P<int32_t>(v[9], I32, cap, "req.vec_count", r);
   o.rel_zxid = P<int64_t>(v[10], I64, cap, "req.rel_zxid", r);
   o.cap = cap;
+  return o;
+}
+
+// [opcode, xid, err, node, zxid, path_off, path_len, slot, sizes,
+//  block_sums], ncap rows (block_sums: one per 256)
+ZkServeOut serve_out(const std::vector<Tensor>& r, int64_t ncap,
+                     const Tensor* ref) {
+  need(r, 10, "serve outputs");
+  ZkServeOut o;
+  o.opcode = P<int32_t>(r[0], I32, ncap, "r.opcode", ref);
+  o.xid = P<int32_t>(r[1], I32, ncap, "r.xid", ref);
+  o.err = P<int32_t>(r[2], I32, ncap, "r.err", ref);
+  o.node = P<int64_t>(r[3], I64, ncap, "r.node", ref);
+  o.zxid = P<int64_t>(r[4], I64, ncap, "r.zxid", ref);
+  o.path_off = P<int64_t>(r[5], I64, ncap, "r.path_off", ref);
+  o.path_len = P<int32_t>(r[6], I32, ncap, "r.path_len", ref);
+  o.slot = P<int64_t>(r[7], I64, ncap, "r.slot", ref);
+  o.sizes = P<int64_t>(r[8], I64, ncap, "r.sizes", ref);
+  o.block_sums = P<int64_t>(r[9], I64, (ncap + 255) / 256, "r.block_sums", ref);
   return o;
 }
 
@@ -602,7 +621,7 @@ void tree_build(const std::vector<Tensor>& t, int64_t n0, int64_t n) {
   hip_ok(zk_tree_build(&s, n0, n, cur_stream()), "tree_build");
 }
 
-// r = [op, xid, err, node, zxid, path_off, path_len, slot, sizes, bsum]
+// r: the serve outputs (serve_out)
 void tree_serve(const std::vector<Tensor>& t, const Tensor& rx,
                 const std::vector<Tensor>& q, const Tensor& n_dev,
                 int64_t ncap, const std::vector<Tensor>& r, int64_t session,
@@ -610,22 +629,10 @@ void tree_serve(const std::vector<Tensor>& t, const Tensor& rx,
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
   ZkReqOut qo = req_out(q, ncap, d);
-  need(r, 10, "serve outputs");
-  const int64_t nb = (ncap + 255) / 256;
-  hip_ok(zk_tree_serve(
-             &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(r[0], I32, ncap, "r.opcode", d),
-             P<int32_t>(r[1], I32, ncap, "r.xid", d),
-             P<int32_t>(r[2], I32, ncap, "r.err", d),
-             P<int64_t>(r[3], I64, ncap, "r.node", d),
-             P<int64_t>(r[4], I64, ncap, "r.zxid", d),
-             P<int64_t>(r[5], I64, ncap, "r.path_off", d),
-             P<int32_t>(r[6], I32, ncap, "r.path_len", d),
-             P<int64_t>(r[7], I64, ncap, "r.slot", d),
-             P<int64_t>(r[8], I64, ncap, "r.sizes", d),
-             P<int64_t>(r[9], I64, nb, "r.block_sums", d), session, now_ms,
-             cur_stream()),
+  ZkServeOut ro = serve_out(r, ncap, d);
+  hip_ok(zk_tree_serve(&s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
+                       P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro,
+                       session, now_ms, cur_stream()),
          "tree_serve");
 }
 
@@ -640,26 +647,15 @@ void tree_serve_frames(const std::vector<Tensor>& t, const Tensor& rx,
                        const c10::optional<Tensor>& seqno, bool read_only) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
-  need(r, 10, "serve outputs");
+  ZkServeOut ro = serve_out(r, ncap, d);
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
   TORCH_CHECK(wslot >= -1 && wslot < 64, "zkmi: watcher slot -1..63");
-  const int64_t nb = (ncap + 255) / 256;
   hip_ok(zk_tree_serve_frames(
              &s, P<uint8_t>(rx, U8, 1, "rx", d),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(r[0], I32, ncap, "r.opcode", d),
-             P<int32_t>(r[1], I32, ncap, "r.xid", d),
-             P<int32_t>(r[2], I32, ncap, "r.err", d),
-             P<int64_t>(r[3], I64, ncap, "r.node", d),
-             P<int64_t>(r[4], I64, ncap, "r.zxid", d),
-             P<int64_t>(r[5], I64, ncap, "r.path_off", d),
-             P<int32_t>(r[6], I32, ncap, "r.path_len", d),
-             P<int64_t>(r[7], I64, ncap, "r.slot", d),
-             P<int64_t>(r[8], I64, ncap, "r.sizes", d),
-             P<int64_t>(r[9], I64, nb, "r.block_sums", d), session, now_ms,
-             (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, session,
+             now_ms, (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
              read_only ? 1 : 0, cur_stream()),
          "tree_serve_frames");
 }
@@ -691,7 +687,7 @@ void tree_serve_ordered(const std::vector<Tensor>& t, const Tensor& rx,
   const Tensor* d = &t[0];
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
   ZkReqOut qo = req_out(q, ncap, d);
-  need(r, 10, "serve outputs");
+  ZkServeOut ro = serve_out(r, ncap, d);
   TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
   const int64_t need_ws = zk_tree_order_workspace(ncap);
   uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
@@ -707,21 +703,10 @@ void tree_serve_ordered(const std::vector<Tensor>& t, const Tensor& rx,
                 "zkmi: scratch must start 16-aligned past the tree's slab");
     snap_cap = sc.numel();
   }
-  const int64_t nb = (ncap + 255) / 256;
   hip_ok(zk_tree_serve_ordered(
              &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(r[0], I32, ncap, "r.opcode", d),
-             P<int32_t>(r[1], I32, ncap, "r.xid", d),
-             P<int32_t>(r[2], I32, ncap, "r.err", d),
-             P<int64_t>(r[3], I64, ncap, "r.node", d),
-             P<int64_t>(r[4], I64, ncap, "r.zxid", d),
-             P<int64_t>(r[5], I64, ncap, "r.path_off", d),
-             P<int32_t>(r[6], I32, ncap, "r.path_len", d),
-             P<int64_t>(r[7], I64, ncap, "r.slot", d),
-             P<int64_t>(r[8], I64, ncap, "r.sizes", d),
-             P<int64_t>(r[9], I64, nb, "r.block_sums", d), session, now_ms,
-             w, ws.numel(), (int32_t)passes, snap_base, snap_cap,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, session,
+             now_ms, w, ws.numel(), (int32_t)passes, snap_base, snap_cap,
              (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
              cur_stream()),
          "tree_serve_ordered");
@@ -771,7 +756,7 @@ void watch_resume(const std::vector<Tensor>& t, const Tensor& rx,
          "watch_resume");
 }
 
-// SEQUENTIAL numbers in stream order (tree.hip seq_*): workspace bytes for
+// SEQUENTIAL numbers in stream order (tree_seq.hip): workspace bytes for
 // ncap requests (zero the first tree_seq_zeroed(ncap) once), then per batch
 // the ordering of the request frames -> seqno (int64 [ncap]) for the serve.
 int64_t tree_seq_workspace(int64_t n) {
@@ -839,8 +824,8 @@ void tree_digest(const std::vector<Tensor>& t, const Tensor& out) {
          "tree_digest");
 }
 
-// GET_CHILDREN / GET_CHILDREN2 batches served from the tree (tree.hip
-// list_*): workspace bytes for ncap requests, then per batch the request
+// GET_CHILDREN / GET_CHILDREN2 batches served from the tree
+// (tree_list.hip): workspace bytes for ncap requests, then per batch the request
 // frames -> the framed replies in out[:total], their starts in rec_off.
 // want: int32 per node slot, all 0x7fffffff (the kernels leave it so).
 int64_t tree_list_workspace(int64_t n) {

@@ -619,7 +619,7 @@ def test_serve_list_with_bad_frames_in_the_batch(gpu, monkeypatch):
 @pytest.mark.parametrize('plen', [0, 1, 255, 256, 4096, 70000])
 def test_path_lengths(gpu, plen):
     """Well-formed requests whose path is 0 .. 70 000 bytes long (the packed
-    path word of tree.hip keeps 24 bits of length, 16 MiB, the frame cap):
+    path word of zk_tree.h keeps 24 bits of length, 16 MiB, the frame cap):
     GET_DATA and EXISTS answer NO_NODE; a CREATE either succeeds and reads
     back, path and data, or fails and leaves the tree as it was."""
     tree, srv = _replica(gpu)

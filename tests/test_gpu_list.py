@@ -1,4 +1,4 @@
-"""The GPU server's list path (csrc/kernels/tree.hip list_*,
+"""The GPU server's list path (csrc/kernels/tree_list.hip,
 GpuServer.serve_list): GET_CHILDREN / GET_CHILDREN2 batches answered from
 the HBM tree by a join of the requested parents against a sweep of the node
 table.  Replies are decoded with the jute oracle and compared, as sorted

@@ -1,5 +1,6 @@
-"""ZooKeeper watches in the GPU server (csrc/kernels/tree.hip wt_*):
-reads with watch=1 arm one-shot watches per watcher slot, writes fire
+"""ZooKeeper watches in the GPU server (csrc/kernels/zk_tree.h wt_*,
+tree_watch.hip): reads with watch=1 arm one-shot watches per watcher slot,
+writes fire
 NodeDataChanged / NodeCreated / NodeDeleted / NodeChildrenChanged as xid -1
 notification frames (K13), and SET_WATCHES catches a resumed session up.
 

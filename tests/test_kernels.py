@@ -995,7 +995,7 @@ def test_gpu_sequential_replicas_agree(gpu):
 def test_gpu_expiry_reclaims_tombstones(gpu):
     """Never-reused SEQUENTIAL names do not fill the hash index: session
     expiry empties the entries it tombstones when nothing after them
-    continues a probe chain (tree.hip ht_reclaim), and the next batch's
+    continues a probe chain (zk_tree.h ht_reclaim), and the next batch's
     names take over the tombstones their probes pass (tree_insert<true>),
     so the tombstone count settles instead of growing until a rebuild."""
     from zkmi.bench.synthetic import GpuServer

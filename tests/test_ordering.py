@@ -1,4 +1,4 @@
-"""In-batch ordering of the GPU server (csrc/kernels/tree.hip tree_order_*,
+"""In-batch ordering of the GPU server (csrc/kernels/tree_order.hip,
 zk_tree_serve_ordered) against the fake server applying the same requests
 one by one.
 

@@ -91,6 +91,53 @@ def test_bad_tensors_raise_on_gpu(gpu):
 
 
 @pytest.mark.gpu
+def test_serve_outputs_checked(gpu):
+    """The three serve ops check their ten output tensors through one
+    helper (serve_out): a short list, a short tensor and a wrong dtype raise
+    the same message from each, before any launch."""
+    from zkmi.bench.synthetic import GpuTree
+    from zkmi.ops import batch as B
+    ops = _lib.lib()
+    ncap = 4
+    tree = GpuTree(100, 16, fanout=10, device=gpu)
+    rx = torch.zeros(64, dtype=torch.uint8, device=gpu)
+    q = B.alloc_request_table(ncap, gpu).tensors()
+    foff = torch.zeros(ncap, dtype=torch.int64, device=gpu)
+    flen = torch.zeros(ncap, dtype=torch.int32, device=gpu)
+    count = torch.zeros(1, dtype=torch.int64, device=gpu)
+    ows = torch.empty(ops.tree_order_workspace(ncap), dtype=torch.uint8,
+                      device=gpu)
+
+    def outputs():
+        # [op, xid, err, node, zxid, path_off, path_len, slot, sizes, bsum]
+        i64 = (3, 4, 5, 7, 8, 9)
+        return [torch.empty(ncap, dtype=torch.int64 if k in i64
+                            else torch.int32, device=gpu) for k in range(10)]
+
+    calls = {
+        'tree_serve': lambda r: ops.tree_serve(
+            tree.tensors, rx, q, count, ncap, r, 1, 0),
+        'tree_serve_frames': lambda r: ops.tree_serve_frames(
+            tree.tensors, rx, foff, flen, count, ncap, r, 1, 0),
+        'tree_serve_ordered': lambda r: ops.tree_serve_ordered(
+            tree.tensors, rx, q, count, ncap, r, 1, 0, ows, 1, None),
+    }
+    short = outputs()
+    short[2] = short[2][:3]
+    wide = outputs()
+    wide[1] = wide[1].to(torch.int64)
+    cases = ((outputs()[:9], 'serve outputs needs 10'),
+             (short, 'r.err has'), (wide, 'r.xid must be Int'))
+    for r, match in cases:
+        said = set()
+        for call in calls.values():
+            with pytest.raises(RuntimeError, match=match) as e:
+                call(r)
+            said.add(str(e.value).splitlines()[0])
+        assert len(said) == 1, said
+
+
+@pytest.mark.gpu
 def test_ops_run_on_the_current_stream(gpu):
     """A scan issued under ``torch.cuda.stream(s)`` is ordered on ``s``."""
     from zkmi.ops import batch as B

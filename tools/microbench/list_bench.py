@@ -1,5 +1,5 @@
 """List-path microbenchmark: GET_CHILDREN2 batches served from the HBM tree
-(csrc/kernels/tree.hip list_*, GpuServer.serve_list) on a 1M-znode tree with
+(csrc/kernels/tree_list.hip, GpuServer.serve_list) on a 1M-znode tree with
 1000 children a directory.  Three batches:
 
   distinct   one request per directory, up to 1024 (1000 on this tree)

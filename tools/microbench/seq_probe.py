@@ -1,5 +1,5 @@
 """Where seq_group_k's time goes on the storm step (BASELINE config 5): the
-kernel's per-chunk phase clocks (csrc/kernels/tree.hip, zk_tree_seq_debug),
+kernel's per-chunk phase clocks (csrc/kernels/tree_seq.hip, zk_tree_seq_debug),
 summarised over the 1024-request chunks of one numbering pass.
 
   python tools/microbench/seq_probe.py [--steps 6]

@@ -6,7 +6,7 @@ never-reused SEQUENTIAL names is seen directly.
   python tools/microbench/storm_census.py --steps 1000 --hash-factor 2
 
 The storm runs with no index rebuild (its expiry reclaims the index,
-csrc/kernels/tree.hip ht_shift); ``rehashes`` counts any that happen.
+csrc/kernels/zk_tree.h ht_shift); ``rehashes`` counts any that happen.
 """
 import argparse
 import os

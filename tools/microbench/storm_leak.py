@@ -1,6 +1,6 @@
 """Storm leak hunt (small tree): after every expiry, any node still owned
 by the expired session is located in the hash index from its home slot,
-with what lies between (tree.hip 64-byte entries: key, val, ...)."""
+with what lies between (zk_tree.h 64-byte entries: key, val, ...)."""
 import os
 import sys
 

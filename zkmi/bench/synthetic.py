@@ -59,7 +59,7 @@ def _next_pow2(x):
     return p
 
 
-NODE_FREE = -2           # node_parent of an unused node (tree.hip)
+NODE_FREE = -2           # node_parent of an unused node (zk_tree.h)
 
 
 def path_owner(paths, world):
@@ -197,7 +197,7 @@ class GpuTree(object):
         # storm's replicated tree at 8 ranks holds ~25M node slots)
         hcap = max(min(_next_pow2(hash_factor * cap), 1 << 28),
                    _next_pow2(2 * cap))
-        # 64-byte entries, empty = all zero bytes (csrc/kernels/tree.hip)
+        # 64-byte entries, empty = all zero bytes (csrc/kernels/zk_tree.h)
         self.ht = torch.zeros(_lib.HT_WORDS * hcap, dtype=I64, device=dev)
         cnt = [0] * _lib.TC_N
         cnt[_lib.TC_NODES], cnt[_lib.TC_ZXID] = nst, nst
@@ -228,7 +228,7 @@ class GpuTree(object):
                          self.pzxid, self.dirty, self.dirty_list,
                          self.node_pw, self.node_path_cap, self.eph]
         # watch table (watch_cap > 0): path-keyed one-shot watches of up to
-        # 64 watcher slots (csrc/kernels/tree.hip wt_*); every serve of a
+        # 64 watcher slots (csrc/kernels/zk_tree.h wt_*); every serve of a
         # tree with one fires the watches its writes hit
         self.watch = None
         if watch_cap > 0:
@@ -377,7 +377,7 @@ class GpuServer(object):
         self.tree = tree
         self.window = window              # K1 entry window of the requests
         # SEQUENTIAL creates numbered in stream order before each serve
-        # (csrc/kernels/tree.hip seq_*: five launches); a server whose
+        # (csrc/kernels/tree_seq.hip: five launches); a server whose
         # batches never carry one (the GET pipeline, the write mixes
         # without SEQUENTIAL) skips them.  Off, a SEQUENTIAL create still
         # gets a unique number, in arrival order.
@@ -472,7 +472,7 @@ class GpuServer(object):
 
     def _resume(self, rx, ft, wslot):
         """SET_WATCHES catch-up of the batch's SET_WATCHES frames for
-        watcher ``wslot`` (csrc/kernels/tree.hip wt_resume_k): events for
+        watcher ``wslot`` (csrc/kernels/tree_watch.hip wt_resume_k): events for
         what changed after relZxid, encoded with the request bytes as path
         arena; the other watches are re-armed."""
         L = _lib.lib()
@@ -570,7 +570,7 @@ class GpuServer(object):
                    out=None):
         """Serve a batch of list requests — GET_CHILDREN / GET_CHILDREN2
         frames only, ``rx[:n]`` (``n`` a host length or a device total) —
-        from the tree (csrc/kernels/tree.hip list_*: two sweeps of the node
+        from the tree (csrc/kernels/tree_list.hip: two sweeps of the node
         table per batch, no child links).  Returns ``(out, total, err,
         frame_table)`` like :meth:`serve`; the replies are in request order.
 
@@ -1497,7 +1497,7 @@ class StormPipeline(object):
     Every check (replies, handshake outcome, ids, password, removed count)
     runs on the device; a step makes no device-to-host read.  The hash
     index needs no rebuild: the expiry moves live entries back over the
-    holes it leaves and empties the rest (csrc/kernels/tree.hip ht_shift),
+    holes it leaves and empties the rest (csrc/kernels/zk_tree.h ht_shift),
     and the next batch's names take over the tombstones their probes pass,
     so never-reused SEQUENTIAL names leave a bounded number of tombstones
     (~0.6 % of the index at the bench's size,

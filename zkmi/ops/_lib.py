@@ -32,7 +32,7 @@ SLOT_DATA = 76
 SC_NEW, SC_RESUMED, SC_EXPIRED, SC_REFUSED, SC_BAD, SC_FULL = range(6)
 CR_RESP_BYTES = 41
 
-# ZkTree counters (csrc/kernels/tree.hip TC_*)
+# ZkTree counters (csrc/kernels/zk_tree.h TC_*)
 TC_NODES, TC_ZXID, TC_PATH_TOP, TC_SLAB_TOP = 0, 1, 2, 3
 TC_FREE_HEAD, TC_FREE_TAIL, TC_FREE_PUB, TC_DIRTY = 4, 5, 6, 7
 TC_SESS, TC_N = 8, 9
@@ -93,7 +93,7 @@ def set_scan_mode(mode):
     return lib().scan_set_mode(mode)
 
 
-# idle value of the list path's per-node claim words (tree.hip LS_NONE)
+# idle value of the list path's per-node claim words (tree_list.hip LS_NONE)
 LIST_IDLE = 0x7fffffff
 
 
@@ -106,7 +106,7 @@ def tree_list_workspace(ncap):
 def tree_list(tree, rx, frame_off, frame_len, count, ncap, wslot, max_frame,
               want, ws, out, out_cap, rec_off, total, err, terminate=False):
     """Serve a batch of GET_CHILDREN / GET_CHILDREN2 frames from the HBM
-    tree (csrc/kernels/tree.hip list_*), on the current stream: the framed
+    tree (csrc/kernels/tree_list.hip), on the current stream: the framed
     replies in request order -> ``out[:total]``, their starts ->
     ``rec_off``.  ``want``: int32 per node slot, all :data:`LIST_IDLE`
     between calls (the kernels put it back).  ``err`` 2 and ``total`` 0:
