@@ -157,6 +157,26 @@ struct ZkSessionTable {
   int64_t span;
 };
 
+// ACL store beside the tree (tree_acl.hip).  ZkTree itself keeps no ACL: a
+// CREATE's vector is interned here by a pass after the serve, and GET_ACL
+// batches read node_acl -> arena.
+struct ZkAclTable {
+  // [cap] per node: arena offset << 24 | byte length of its ACL vector in
+  // wire format (be32 count + entries); -1: lost (the store was full)
+  int64_t* node_acl;
+  int64_t cap;
+  uint8_t* arena;     // the interned vectors, each once; the open ACL at 0
+  int64_t arena_cap;
+  // intern index (open addressing, create time only): content hash | 1
+  // (0 = empty) -> the vector's arena word (0 = being published, -1 = lost)
+  int64_t* key;       // [hmask + 1]
+  int64_t* val;       // [hmask + 1]
+  int64_t hmask;
+  // [8] arena top, entries, nodes bound lost, the arena top after the last
+  // record pass, the entry limit
+  int64_t* ctr;
+};
+
 // ---- launchers (stream-ordered; return 0 or a hipError_t) ----------------
 int64_t zk_scan_workspace(int64_t n);
 int zk_scan_set_mode(int mode);
@@ -275,6 +295,20 @@ int zk_tree_list(const ZkTree*, const uint8_t*, const int64_t*,
                  const int32_t*, const int64_t*, int64_t, int32_t, int64_t,
                  int32_t*, uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
                  int64_t*, int32_t*, int32_t, hipStream_t);
+// The ACL path (tree_acl.hip): bytes of the workspace for ncap requests
+// (both passes share it); the record pass after a serve (frames, count, ncap,
+// the serve's r_op / r_err / r_node, workspace + bytes); the GET_ACL serve
+// (frames, count, ncap, workspace + bytes, out + capacity, rec_off[ncap],
+// total, err, terminate), with zk_tree_list's conventions
+int64_t zk_tree_acl_workspace(int64_t ncap);
+int zk_tree_acl_record(const ZkAclTable*, const uint8_t*, const int64_t*,
+                       const int32_t*, const int64_t*, int64_t,
+                       const int32_t*, const int32_t*, const int64_t*,
+                       uint8_t*, int64_t, hipStream_t);
+int zk_tree_acl_get(const ZkTree*, const ZkAclTable*, const uint8_t*,
+                    const int64_t*, const int32_t*, const int64_t*, int64_t,
+                    uint8_t*, int64_t, uint8_t*, int64_t, int64_t*, int64_t*,
+                    int32_t*, int32_t, hipStream_t);
 int zk_bench_gen_get(int64_t, uint64_t, int64_t, int64_t, int32_t,
                      const int64_t*, int64_t*, int32_t*, int64_t*, int32_t*,
                      const int64_t*, int64_t*, int64_t*, hipStream_t);
@@ -332,6 +366,9 @@ static_assert(sizeof(ZkReplyOut) == 12 * 8, "ZkReplyOut layout");
 static_assert(sizeof(ZkReqOut) == 12 * 8, "ZkReqOut layout");
 static_assert(sizeof(ZkServeOut) == 10 * 8, "ZkServeOut layout");
 static_assert(sizeof(ZkSessionTable) == 7 * 8, "ZkSessionTable layout");
+static_assert(sizeof(ZkAclTable) == 8 * 8, "ZkAclTable layout");
+static_assert(offsetof(ZkAclTable, arena) == 2 * 8, "ZkAclTable.arena");
+static_assert(offsetof(ZkAclTable, hmask) == 6 * 8, "ZkAclTable.hmask");
 static_assert(sizeof(ZkTree) == 27 * 8, "ZkTree layout");
 static_assert(offsetof(ZkTree, store) == 9 * 8, "ZkTree.store");
 static_assert(offsetof(ZkTree, free_list) == 14 * 8, "ZkTree.free_list");

@@ -157,6 +157,25 @@ ZkTree tree(const std::vector<Tensor>& v) {
   return t;
 }
 
+// [node_acl, arena, key, val, ctr]; sizes give the caps and the index mask
+ZkAclTable acl_table(const std::vector<Tensor>& v, const Tensor* r) {
+  need(v, 5, "acl table");
+  ZkAclTable a;
+  a.cap = v[0].numel();
+  a.node_acl = P<int64_t>(v[0], I64, 1, "acl.node_acl", r);
+  a.arena_cap = v[1].numel();
+  // (the open ACL's 27 bytes sit at offset 0)
+  a.arena = P<uint8_t>(v[1], U8, 27, "acl.arena", r);
+  const int64_t h = v[2].numel();
+  TORCH_CHECK(h > 0 && (h & (h - 1)) == 0,
+              "zkmi: acl.key must hold a power of two of entries");
+  a.key = P<int64_t>(v[2], I64, h, "acl.key", r);
+  a.val = P<int64_t>(v[3], I64, h, "acl.val", r);
+  a.hmask = h - 1;
+  a.ctr = P<int64_t>(v[4], I64, 8, "acl.ctr", r);
+  return a;
+}
+
 // [xid, err, opcode, status, zxid, stat64 [6, cap], stat32 [5, cap],
 //  pay_off, pay_len, aux0, aux1]
 ZkReplyOut reply_out(const std::vector<Tensor>& v, int64_t cap,
@@ -863,6 +882,74 @@ void tree_list(const std::vector<Tensor>& t, const Tensor& rx,
          "tree_list");
 }
 
+// The ACL path (tree_acl.hip).  acl: the table's tensor list (acl_table);
+// one workspace of tree_acl_workspace(ncap) bytes serves both ops.
+int64_t tree_acl_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_acl_workspace n");
+  return zk_tree_acl_workspace(n);
+}
+
+uint8_t* acl_ws(const Tensor& ws, int64_t ncap, const Tensor* d) {
+  uint8_t* w = P<uint8_t>(ws, U8, zk_tree_acl_workspace(ncap),
+                          "acl workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w) % 16 == 0,
+              "zkmi: acl workspace must be 16-byte aligned");
+  return w;
+}
+
+// After a serve, on its stream: the ACLs of the batch's successful CREATEs
+// (r_op / r_err / r_node: the serve's reply descriptors) interned and bound
+// to their nodes.
+void tree_acl_record(const std::vector<Tensor>& acl, const Tensor& rx,
+                     const Tensor& foff, const Tensor& flen,
+                     const Tensor& n_dev, int64_t ncap, const Tensor& r_op,
+                     const Tensor& r_err, const Tensor& r_node,
+                     const Tensor& ws) {
+  TORCH_CHECK(!acl.empty(), "zkmi: acl table needs 5 tensors, got 0");
+  const Tensor* d = &acl[0];
+  ZkAclTable a = acl_table(acl, d);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: tree_acl ncap");
+  hip_ok(zk_tree_acl_record(
+             &a, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(r_op, I32, ncap, "r.opcode", d),
+             P<int32_t>(r_err, I32, ncap, "r.err", d),
+             P<int64_t>(r_node, I64, ncap, "r.node", d),
+             acl_ws(ws, ncap, d), ws.numel(), cur_stream()),
+         "tree_acl_record");
+}
+
+// GET_ACL batches served from the tree and its ACL table: the request
+// frames -> the framed replies in out[:total], their starts in rec_off.
+void tree_acl_get(const std::vector<Tensor>& t,
+                  const std::vector<Tensor>& acl, const Tensor& rx,
+                  const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
+                  int64_t ncap, const Tensor& ws, const Tensor& out,
+                  int64_t out_cap, const Tensor& rec_off, const Tensor& total,
+                  const Tensor& err, bool terminate) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a = acl_table(acl, d);
+  TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+              " elements, needs ", s.store.cap);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 28), "zkmi: tree_acl ncap");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_acl_get out_cap");
+  hip_ok(zk_tree_acl_get(
+             &s, &a, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             acl_ws(ws, ncap, d), ws.numel(),
+             P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_acl_get");
+}
+
 void tree_expire(const std::vector<Tensor>& t, int64_t session, int64_t ncap,
                  const Tensor& removed) {
   ZkTree s = tree(t);
@@ -1239,6 +1326,16 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
         "bool terminate=False) -> ()",
         &tree_list);
+  m.def("tree_acl_workspace(int n) -> int", &tree_acl_workspace);
+  m.def("tree_acl_record(Tensor(a!)[] acl, Tensor rx, Tensor frame_off, "
+        "Tensor frame_len, Tensor count, int ncap, Tensor r_op, "
+        "Tensor r_err, Tensor r_node, Tensor(b!) ws) -> ()",
+        &tree_acl_record);
+  m.def("tree_acl_get(Tensor[] tree, Tensor[] acl, Tensor rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor(a!) ws, Tensor(b!) out, int out_cap, Tensor(c!) rec_off, "
+        "Tensor(d!) total, Tensor(e!) err, bool terminate=False) -> ()",
+        &tree_acl_get);
   m.def("watch_events(Tensor r_op, Tensor r_err, Tensor count, int ncap, "
         "Tensor fired, Tensor(a!) bsum, Tensor(b!) ev_slot, "
         "Tensor(c!) ev_type, Tensor(d!) ev_path_off, Tensor(e!) ev_path_len, "

@@ -99,7 +99,8 @@ class GpuTree(object):
     def __init__(self, n_nodes=1_000_000, data_bytes=100, fanout=1000,
                  device=None, spare=0.25, seed=0, shard=None, ctime_ms=None,
                  data_dist=None, name_pad=None, scratch=0, watch_cap=0,
-                 hash_factor=2, compact_free=False):
+                 hash_factor=2, compact_free=False, acl_cap=0,
+                 acl_arena_bytes=None):
         dev = torch.device(device) if device is not None else \
             torch.device('cuda', torch.cuda.current_device())
         self.device = dev
@@ -236,6 +237,12 @@ class GpuTree(object):
             self.watch = (torch.zeros(wh, dtype=I64, device=dev),
                           torch.zeros(2 * wh, dtype=I64, device=dev))
             self._tensors = self._tensors + list(self.watch)
+        # ACL table (acl_cap > 0: room for that many distinct ACLs beside the
+        # open one): csrc/kernels/tree_acl.hip.  A server over a tree with
+        # one records every CREATE's ACL and serves GET_ACL batches
+        self.acl = None
+        if acl_cap > 0:
+            self._init_acl(int(acl_cap), acl_arena_bytes)
         now = int(time.time() * 1000) if ctime_ms is None else ctime_ms
         L.tree_fill(self._tensors, 0, nst, nk, now)
         # shard = (rank, world): this replica indexes only the leaves whose
@@ -253,6 +260,49 @@ class GpuTree(object):
     def tensors(self):
         """The descriptor list of the tree for torch.ops.zkmi."""
         return self._tensors
+
+    def _init_acl(self, acl_cap, arena_bytes):
+        """The ACL table's tensors (zk_abi.h ZkAclTable, in the order
+        csrc/torch/zkmi_ops.cpp acl_table() takes): a word per node, the
+        arena of interned wire-format vectors, the intern index and the
+        counters.  ZooKeeper's open ACL sits at arena offset 0 and every
+        node starts bound to it (the static nodes answer it, as fakezk's
+        pre-made nodes do).  ``arena_bytes`` defaults to 64 per ACL (the
+        mix's two-entry digest ACL is 83 bytes, the open one 27)."""
+        from .. import jute
+        dev = self.device
+        raw = B._acl_bytes(jute.DEFAULT_ACL)
+        if arena_bytes is None:
+            arena_bytes = 64 * acl_cap + 256
+        arena_bytes = max(int(arena_bytes), len(raw))
+        word = len(raw)                       # offset 0 << 24 | length
+        node_acl = torch.full((self.cap,), word, dtype=I64, device=dev)
+        arena = torch.zeros(arena_bytes, dtype=U8, device=dev)
+        arena[:len(raw)] = torch.frombuffer(bytearray(raw), dtype=U8).to(dev)
+        hcap = _next_pow2(2 * (acl_cap + 1))
+        key = np.zeros(hcap, np.int64)
+        val = np.zeros(hcap, np.int64)
+        h = _lib.acl_hash(raw)
+        s = (h >> 8) & (hcap - 1)
+        key[s], val[s] = _i64(h), word
+        ctr = [0] * 8
+        ctr[_lib.AC_TOP] = ctr[_lib.AC_OLD_TOP] = len(raw)
+        ctr[_lib.AC_ENT] = 1
+        ctr[_lib.AC_LIMIT] = acl_cap + 1
+        self.acl = [node_acl, arena, torch.from_numpy(key).to(dev),
+                    torch.from_numpy(val).to(dev),
+                    torch.tensor(ctr, dtype=I64, device=dev)]
+
+    def acl_host(self, v):
+        """The decoded ACL of node ``v`` read back from the ACL table, or
+        None for a lost binding (host readback; tests)."""
+        from .. import jute
+        w = int(self.acl[0][v].item())
+        if w == _lib.ACL_LOST:
+            return None
+        off, ln = w >> 24, w & 0xFFFFFF
+        raw = bytes(self.acl[1][off:off + ln].cpu().numpy().tobytes())
+        return jute.JuteReader(raw, 0).read_acl()
 
     def expire(self, session, removed=None):
         """Delete every ephemeral node owned by ``session`` (server side of
@@ -507,7 +557,12 @@ class GpuServer(object):
         ``passes`` requests in the batch has the excess answered
         SYSTEMERROR, see :meth:`order_stats`).  Reads and sets followed by
         a write to their path snapshot their reply into the tree's
-        ``scratch``.  Without it requests of a batch are concurrent."""
+        ``scratch``.  Without it requests of a batch are concurrent.
+
+        On a tree with an ACL table (``GpuTree(acl_cap=...)``) every
+        successful CREATE's ACL is recorded after the serve (two launches,
+        csrc/kernels/tree_acl.hip).  A GET_ACL in the batch is answered
+        UNIMPLEMENTED here: GET_ACL batches go through :meth:`serve_acl`."""
         for _ in self.serve_steps(rx, n, session, terminate, ordered, passes,
                                   wslot, resume):
             pass
@@ -551,6 +606,11 @@ class GpuServer(object):
             L.tree_finish_scan(self.tree.tensors, ft.count, 0, True,
                                self.cap_frames, self.presized[1],
                                self.total_err[0])
+        if self.tree.acl is not None and not self.read_only:
+            # the batch's successful CREATEs bind their ACLs
+            _lib.tree_acl_record(self.tree.acl, rx, ft.off, ft.length,
+                                 ft.count, self.cap_frames, r.opcode, r.err,
+                                 r.node, self._acl_workspace())
         out, rec_off, total, err = B.encode_responses(
             r, self.tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
@@ -615,6 +675,64 @@ class GpuServer(object):
         self.last_rec_off = self.list_rec_off
         self.result = (out, total, err, ft)
         return self.result
+
+    def _acl_workspace(self):
+        if getattr(self, 'acl_ws', None) is None:
+            self.acl_ws = torch.empty(
+                _lib.tree_acl_workspace(self.cap_frames), dtype=U8,
+                device=self.tree.device)
+        return self.acl_ws
+
+    def serve_acl(self, rx, n, terminate=False, out=None):
+        """Serve a batch of GET_ACL frames, ``rx[:n]`` (``n`` a host length
+        or a device total), from the tree and its ACL table
+        (csrc/kernels/tree_acl.hip).  Returns ``(out, total, err,
+        frame_table)`` like :meth:`serve`; the replies are in request order:
+        the node's ACL as its CREATE sent it (the open ACL for the static
+        nodes), then its Stat.
+
+        Any other op in the batch is answered UNIMPLEMENTED, a truncated
+        frame BAD_ARGUMENTS, a missing path NO_NODE (``/`` included: it has
+        no node in this tree), and a node whose ACL found no room in the
+        table SYSTEMERROR (see :meth:`acl_stats`); all header only.  ``err``
+        2 with ``total`` 0: the replies did not fit ``out`` (default: the
+        server's reply buffer) and nothing was written.  Mixed batches go
+        through :meth:`serve`, which answers GET_ACL UNIMPLEMENTED.
+
+        Raises ``ValueError`` on a tree without an ACL table."""
+        tree = self.tree
+        if tree.acl is None:
+            raise ValueError('serve_acl: the tree keeps no ACL table '
+                             '(GpuTree(acl_cap=...))')
+        dev = tree.device
+        if getattr(self, 'acl_rec_off', None) is None:
+            self.acl_rec_off = torch.empty(self.cap_frames, dtype=I64,
+                                           device=dev)
+            self.acl_total_err = B._total_err(dev)
+        if out is None:
+            out = self.out
+        ft = self.scanner.scan(rx, n)
+        total, err = self.acl_total_err
+        _lib.tree_acl_get(tree.tensors, tree.acl, rx, ft.off, ft.length,
+                          ft.count, self.cap_frames, self._acl_workspace(),
+                          out, out.numel(), self.acl_rec_off, total, err,
+                          terminate)
+        self.last_rec_off = self.acl_rec_off
+        self.result = (out, total, err, ft)
+        return self.result
+
+    def acl_stats(self):
+        """(entries, arena bytes used, lost) of the tree's ACL table: the
+        distinct ACLs stored (the open one included), the bytes they take
+        (the whole arena once a vector did not fit: the arena is a bump
+        allocator), and the created nodes whose ACL found no room (they
+        answer GET_ACL with SYSTEMERROR).  One host read."""
+        acl = self.tree.acl
+        if acl is None:
+            raise ValueError('acl_stats: the tree keeps no ACL table')
+        c = acl[4].cpu().tolist()
+        return (c[_lib.AC_ENT], min(c[_lib.AC_TOP], acl[1].numel()),
+                c[_lib.AC_LOST])
 
     def _seq_order(self, rx, ft):
         """Number the batch's SEQUENTIAL creates in stream order (parent's
@@ -955,6 +1073,139 @@ class ListPipeline(object):
                 'want_children': self.want_children,
                 'string_bytes': int(rep.pay_len.sum().item()),
                 'want_bytes': self.want_bytes, 'bad': int(self.bad.item())}
+
+
+class AclPipeline(object):
+    """Batched getACL() over the synthetic tree: ``batch`` GET_ACL requests
+    on live leaves drawn at random (with ``seed``) when the pipeline is
+    built; the tree needs an ACL table (``GpuTree(acl_cap=...)``).
+
+    A step is the K10 encode of the requests, :meth:`GpuServer.serve_acl`,
+    then the client half on the replies: K1, K2-K8 decode, and the ACL
+    vectors expanded to one (perms, scheme, id) row per entry.  The device
+    check adds to ``bad`` every reply that is not a clean OK, whose entry
+    count or whose first entry's perms differ from the node's ACL in the
+    table (read back to the host when the pipeline is built); a good step
+    adds ``batch`` to ``acc``.  No host read inside a step."""
+
+    def __init__(self, tree, batch, seed=0):
+        if tree.acl is None:
+            raise ValueError('AclPipeline: the tree keeps no ACL table')
+        self.tree = tree
+        self.batch = n = batch
+        self.dev = dev = tree.device
+        L = _lib.lib()
+        nn = min(int(tree.counters[_lib.TC_NODES].item()), tree.cap)
+        par = tree.node_parent[:nn].cpu().numpy()
+        live = np.nonzero(par[tree.leaf0:] != NODE_FREE)[0] + tree.leaf0
+        rng = np.random.default_rng(seed + 29)
+        nidx = live[rng.integers(0, len(live), n)]
+        # what each reply must carry: its node's vector in the table
+        words = tree.acl[0][:nn].cpu().numpy()[nidx]
+        arena = tree.acl[1].cpu().numpy().tobytes()
+        cnt = np.zeros(n, np.int32)
+        p0 = np.zeros(n, np.int32)
+        nbytes = np.zeros(n, np.int64)
+        for wd in np.unique(words):
+            if wd == _lib.ACL_LOST:
+                raise ValueError('AclPipeline: a node with a lost ACL')
+            off, ln = int(wd) >> 24, int(wd) & 0xFFFFFF
+            m = words == wd
+            cnt[m] = int.from_bytes(arena[off:off + 4], 'big')
+            p0[m] = int.from_bytes(arena[off + 4:off + 8], 'big')
+            nbytes[m] = ln
+        self.want_cnt = torch.from_numpy(cnt).to(dev)
+        self.want_p0 = torch.from_numpy(p0).to(dev)
+        self.want_entries = int(cnt.sum())
+        frame = 4 + 16 + nbytes + 68
+        out_cap = int(frame.sum()) + 64
+        idx = torch.from_numpy(nidx).to(dev)
+        self.idx = idx
+        self.xt = B.XidTable(bits=max(20, (n - 1).bit_length() + 1),
+                             device=dev)
+        z64 = torch.zeros(n, dtype=I64, device=dev)
+        z32 = torch.zeros(n, dtype=I32, device=dev)
+        self.rb = B.RequestBatch(
+            n, torch.full((n,), consts.OP_CODES['GET_ACL'], dtype=I32,
+                          device=dev),
+            torch.arange(n, dtype=I32, device=dev), z32,
+            tree.node_path_off[idx].contiguous(),
+            tree.node_path_len[idx].contiguous(), z64, z32, z32,
+            tree.path_arena, tree.slab, torch.zeros(1, dtype=I64, device=dev),
+            torch.zeros(1, dtype=I32, device=dev),
+            torch.zeros(16, dtype=U8, device=dev))
+        maxpath = int(tree.node_path_len[idx].max().item())
+        self.tx = torch.empty(n * (16 + maxpath) + 64, dtype=U8, device=dev)
+        self.server = GpuServer(tree, n, out_cap,
+                                window=B.frame_window(16 + maxpath),
+                                seq_order=False)
+        self.rscanner = B.FrameScanner(
+            n, dev, window=B.frame_window(int(frame.max())))
+        self.reply = B.alloc_replies(n, dev)
+        self.reply.aux0.zero_()
+        # one row per ACL entry; an entry is 12 bytes of the reply stream at
+        # least, so this bounds them whatever the replies
+        self.row_cap = out_cap // 12 + 1
+        self.perms = torch.zeros(self.row_cap, dtype=I32, device=dev)
+        self.soff = torch.empty(self.row_cap, dtype=I64, device=dev)
+        self.slen = torch.empty(self.row_cap, dtype=I32, device=dev)
+        self.ioff = torch.empty(self.row_cap, dtype=I64, device=dev)
+        self.ilen = torch.empty(self.row_cap, dtype=I32, device=dev)
+        self.row_base = torch.zeros(n, dtype=I64, device=dev)
+        self.nrows = torch.zeros(1, dtype=I64, device=dev)
+        self.scan_ws = torch.empty(L.scan_workspace(n), dtype=I64, device=dev)
+        self.bad = torch.zeros(1, dtype=I64, device=dev)
+        self.last = None
+
+    def capture(self, acc):
+        """One step as a HIP graph (run an eager step first)."""
+        return _capture_steps(self, acc)
+
+    def encode(self):
+        """The client's request stream (K10): ``(tx, device total)``."""
+        tx, _, total, _ = B.encode_requests(self.rb, self.xt, out=self.tx)
+        return tx, total
+
+    def server_step(self, tx, total):
+        """The server half alone: K1 on the requests and the ACL kernels."""
+        return self.server.serve_acl(tx, _len(total))
+
+    def step(self, validate=True, acc=None):
+        if validate and acc is None:
+            acc = torch.zeros(1, dtype=I64, device=self.dev)
+        L = _lib.lib()
+        n = self.batch
+        tx, total = self.encode()
+        rx, rtotal, rerr, _ = self.server_step(tx, total)
+        ft = self.rscanner.scan(rx, _len(rtotal))
+        rep = self.reply
+        # (rows past the frames K1 found keep a zero count: nothing of a
+        # short stream is expanded)
+        rep.aux0.zero_()
+        B.decode_replies(rx, ft, self.xt, out=rep)
+        L.scan_excl(rep.aux0, self.row_base, self.nrows, self.scan_ws)
+        L.expand_acl(rx, rep.pay_off, rep.aux0, self.row_base, self.perms,
+                     self.soff, self.slen, self.ioff, self.ilen)
+        self.last = (rep, rx, ft, rtotal)
+        if not validate:
+            return None
+        first = self.perms[self.row_base.clamp(0, self.row_cap - 1)]
+        bad = ((rep.err != 0) | (rep.status != 0) |
+               (rep.aux0 != self.want_cnt) | (first != self.want_p0)).sum()
+        bad = bad + (ft.count[0] != n).to(I64) + (rerr[0] != 0).to(I64)
+        bad = bad + (self.nrows[0] != self.want_entries).to(I64)
+        self.bad.add_(bad)
+        acc.add_(n * (bad == 0).to(I64))
+        return acc
+
+    def diagnose(self):
+        """Host view of the last step's replies (after a failed check)."""
+        rep, rx, ft, rtotal = self.last
+        return {'frames': ft.host_result(), 'total': int(rtotal.item()),
+                'err': rep.err.unique().cpu().tolist(),
+                'entries': int(rep.aux0.sum().item()),
+                'want_entries': self.want_entries,
+                'bad': int(self.bad.item())}
 
 
 def _arena(strings, dev):

@@ -116,5 +116,54 @@ def tree_list(tree, rx, frame_off, frame_len, count, ncap, wslot, max_frame,
                     rec_off, total, err, bool(terminate))
 
 
+# ACL table (csrc/kernels/tree_acl.hip): a lost binding, the counter words
+ACL_LOST = -1
+AC_TOP, AC_ENT, AC_LOST, AC_OLD_TOP, AC_LIMIT = 0, 1, 2, 3, 4
+
+
+def acl_hash(raw):
+    """Key of the ACL vector ``raw`` (wire bytes) in the intern index: the
+    host mirror of csrc/kernels/zk_tree.h path_hash, | 1."""
+    m64 = (1 << 64) - 1
+    n = len(raw)
+    h = 0x9E3779B97F4A7C15 ^ n
+    for i in range(0, n, 8):
+        w = int.from_bytes(raw[i:i + 8], 'little')
+        h = ((h ^ w) * 0xFF51AFD7ED558CCD) & m64
+        h ^= h >> 32
+    h ^= h >> 33
+    h = (h * 0xC4CEB9FE1A85EC53) & m64
+    h ^= h >> 33
+    return h | 1
+
+
+def tree_acl_workspace(ncap):
+    """Bytes of the workspace :func:`tree_acl_record` and
+    :func:`tree_acl_get` need for ``ncap`` requests (one uint8 tensor serves
+    both; nothing in it needs zeroing)."""
+    return lib().tree_acl_workspace(int(ncap))
+
+
+def tree_acl_record(acl, rx, frame_off, frame_len, count, ncap, r_op, r_err,
+                    r_node, ws):
+    """After a serve, on its stream: intern the ACL vector of every
+    successful CREATE of the batch (``r_op`` / ``r_err`` / ``r_node``: the
+    serve's reply descriptors) in the table ``acl`` (``GpuTree.acl``) and
+    bind it to the created node.  Two launches, no host read."""
+    lib().tree_acl_record(acl, rx, frame_off, frame_len, count, int(ncap),
+                          r_op, r_err, r_node, ws)
+
+
+def tree_acl_get(tree, acl, rx, frame_off, frame_len, count, ncap, ws, out,
+                 out_cap, rec_off, total, err, terminate=False):
+    """Serve a batch of GET_ACL frames from the HBM tree and its ACL table
+    (csrc/kernels/tree_acl.hip), on the current stream: the framed replies
+    in request order -> ``out[:total]``, their starts -> ``rec_off``.
+    ``err`` 2 and ``total`` 0: the stream did not fit ``out_cap``."""
+    lib().tree_acl_get(tree, acl, rx, frame_off, frame_len, count, int(ncap),
+                       ws, out, int(out_cap), rec_off, total, err,
+                       bool(terminate))
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
