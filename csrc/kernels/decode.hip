@@ -12,6 +12,7 @@
 // coalesced.  Ragged vectors (children, ACL entries, SET_WATCHES paths) are
 // expanded by a second pass after a scan of the per-frame counts.
 #include "zk_common.h"
+#include "zk_frame_rows.h"
 
 namespace zk {
 
@@ -109,16 +110,36 @@ ZK_DEV bool wave_bytes_equal(const uint8_t* a, const uint8_t* b, int32_t n,
   return __ballot(diff != 0) == 0;
 }
 
-template <bool CHECK>
-__global__ __launch_bounds__(DEC_T) void decode_replies_k(
+// TILES: after a rows-deferred K1 scan.  The frame's row comes from the
+// scan's tile lists T (zk_frame_rows.h) instead of the table; the workgroup
+// also writes its rows to the table (rows_off / rows_len, what fs_rows
+// would have written) and clears its share of the scan's flags.
+static_assert(DEC_T == FR_T, "a workgroup per block of FR_T frames");
+template <bool CHECK, bool TILES>
+ZK_DEV void decode_replies_body(
     const uint8_t* __restrict__ buf, const int64_t* __restrict__ foff,
     const int32_t* __restrict__ flen, const int64_t* __restrict__ n_dev,
     int64_t ncap, const int64_t* __restrict__ xid_tab, int64_t xid_mask,
-    ZkReplyOut o, ZkGetCheck chk) {
+    const ZkReplyOut& o, const ZkGetCheck& chk, const ZkFrameTiles* T,
+    int64_t* __restrict__ rows_off, int32_t* __restrict__ rows_len) {
   const uint32_t nwg = gridDim.x;
-  const int64_t i = (int64_t)xcd_remap(blockIdx.x, nwg) * DEC_T + threadIdx.x;
-  const bool live = i < ncap && i < *n_dev;
-  if (!CHECK && !live) return;
+  const uint32_t blk = xcd_remap(blockIdx.x, nwg);
+  const int64_t i = (int64_t)blk * DEC_T + threadIdx.x;
+  bool live = i < ncap && i < *n_dev;
+  int64_t fo = 0;                    // the frame's row
+  int32_t fl = 0;
+  if (TILES) {
+    __shared__ FrLds rows;
+    const int64_t nf = *n_dev;
+    live = fr_row(*T, blk, nf < ncap ? nf : ncap, rows, fo, fl);
+    if (live) {
+      rows_off[i] = fo;
+      rows_len[i] = fl;
+    }
+    fr_housekeep(*T);
+  } else if (!CHECK && !live) {
+    return;
+  }
   int64_t good = 0;
   // the payload sample of this step (read before block 0 advances tick)
   const int64_t salt = CHECK && chk.tick != nullptr ? chk.tick[1] : 0;
@@ -126,8 +147,9 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
   int64_t s_off = 0, s_node = 0;
   int32_t s_len = 0;
   if (live) {
-  const uint8_t* p = buf + foff[i];
-  const int64_t L = flen[i];
+  if (!TILES) fo = foff[i];
+  const uint8_t* p = buf + fo;
+  const int64_t L = TILES ? fl : flen[i];
   int32_t status = ST_OK;
   int32_t op = OP_UNKNOWN;
   int64_t poff = -1;
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
         int32_t dl = ld_be32(b);
         if (dl < 0) dl = 0;
         if (4 + (int64_t)dl + STAT_BYTES > A) { status = ST_BAD_DECODE; break; }
-        poff = foff[i] + 20;
+        poff = fo + 20;
         plen = dl;
         if (tail_ok && 4 + (int64_t)dl + STAT_BYTES == A) read_stat_regs(sw, o, i);
         else read_stat(b + 4 + dl, o, i);
@@ -189,7 +211,7 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
         int32_t l = ld_be32(b);
         if (l < 0) l = 0;
         if (4 + (int64_t)l > A) { status = ST_BAD_DECODE; break; }
-        poff = foff[i] + 20;
+        poff = fo + 20;
         plen = l;
         break;
       }
@@ -207,7 +229,7 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
           status = ST_BAD_DECODE;
           break;
         }
-        poff = foff[i] + 20;
+        poff = fo + 20;
         plen = (int32_t)k;
         a0 = cnt;
         if (op == OP_GET_CHILDREN2) {
@@ -221,7 +243,7 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
         const int32_t cnt = max(ld_be32(b), 0);
         const int64_t k = skip_acl(b + 4, A - 4, cnt);
         if (k < 0 || 4 + k + STAT_BYTES > A) { status = ST_BAD_DECODE; break; }
-        poff = foff[i] + 20;
+        poff = fo + 20;
         plen = (int32_t)k;
         a0 = cnt;
         if (tail_ok && 4 + k + STAT_BYTES == A) read_stat_regs(sw, o, i);
@@ -235,7 +257,7 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
         if (12 + (int64_t)l > A) { status = ST_BAD_DECODE; break; }
         a0 = ld_be32(b);                  // (type / state: accepted rows only)
         a1 = ld_be32(b + 4);
-        poff = foff[i] + 28;
+        poff = fo + 28;
         plen = l;
         break;
       }
@@ -289,6 +311,28 @@ __global__ __launch_bounds__(DEC_T) void decode_replies_k(
       atomicAdd(&chk.acc[blockIdx.x % (uint32_t)chk.slots],
                 (unsigned long long)tot);
   }
+}
+
+template <bool CHECK>
+__global__ __launch_bounds__(DEC_T) void decode_replies_k(
+    const uint8_t* __restrict__ buf, const int64_t* __restrict__ foff,
+    const int32_t* __restrict__ flen, const int64_t* __restrict__ n_dev,
+    int64_t ncap, const int64_t* __restrict__ xid_tab, int64_t xid_mask,
+    ZkReplyOut o, ZkGetCheck chk) {
+  decode_replies_body<CHECK, false>(buf, foff, flen, n_dev, ncap, xid_tab,
+                                    xid_mask, o, chk, nullptr, nullptr,
+                                    nullptr);
+}
+
+template <bool CHECK>
+__global__ __launch_bounds__(DEC_T) void decode_replies_tiles_k(
+    ZkFrameTiles T, int64_t* __restrict__ rows_off,
+    int32_t* __restrict__ rows_len, const int64_t* __restrict__ n_dev,
+    int64_t ncap, const int64_t* __restrict__ xid_tab, int64_t xid_mask,
+    ZkReplyOut o, ZkGetCheck chk) {
+  decode_replies_body<CHECK, true>(T.buf, nullptr, nullptr, n_dev, ncap,
+                                   xid_tab, xid_mask, o, chk, &T, rows_off,
+                                   rows_len);
 }
 
 // Expand string vectors: region (offset of first string) + count per row ->
@@ -433,6 +477,43 @@ int zk_decode_replies_check(const uint8_t* buf, const int64_t* foff,
     return (int)hipErrorInvalidValue;
   zk::decode_replies_k<true><<<zk::nblk(ncap), zk::DEC_T, 0, st>>>(
       buf, foff, flen, n_dev, ncap, xid_tab, xid_mask, *o,
+      zk::ZkGetCheck{idx, xid, data_len, acc, slots, tick, slab, slot_off});
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+// zk_decode_replies / zk_decode_replies_check after a rows-deferred scan
+// (zk_frame_scan flags bit 24): the rows come from the scan's tile lists,
+// and foff / flen [ncap] receive them, so the table ends up as fs_rows
+// would have left it and the scan's workspace is clean for the next scan.
+int zk_decode_replies_tiles(const ZkFrameTiles* tiles, int64_t* foff,
+                            int32_t* flen, const int64_t* n_dev, int64_t ncap,
+                            const int64_t* xid_tab, int64_t xid_mask,
+                            const ZkReplyOut* o, hipStream_t st) {
+  if (ncap <= 0) return (int)hipErrorInvalidValue;  // (the flags stay set)
+  zk::decode_replies_tiles_k<false><<<zk::nblk(ncap), zk::DEC_T, 0, st>>>(
+      *tiles, foff, flen, n_dev, ncap, xid_tab, xid_mask, *o,
+      zk::ZkGetCheck{nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr,
+                     nullptr});
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_decode_replies_check_tiles(const ZkFrameTiles* tiles, int64_t* foff,
+                                  int32_t* flen, const int64_t* n_dev,
+                                  int64_t ncap, const int64_t* xid_tab,
+                                  int64_t xid_mask, const ZkReplyOut* o,
+                                  const int64_t* idx, const int32_t* xid,
+                                  const int32_t* data_len,
+                                  unsigned long long* acc, int32_t slots,
+                                  int64_t* tick, const uint8_t* slab,
+                                  const int64_t* slot_off, hipStream_t st) {
+  if (ncap <= 0) return (int)hipErrorInvalidValue;
+  if (slots < 1 || slots > 64) return (int)hipErrorInvalidValue;
+  if ((slab == nullptr) != (slot_off == nullptr))
+    return (int)hipErrorInvalidValue;
+  zk::decode_replies_tiles_k<true><<<zk::nblk(ncap), zk::DEC_T, 0, st>>>(
+      *tiles, foff, flen, n_dev, ncap, xid_tab, xid_mask, *o,
       zk::ZkGetCheck{idx, xid, data_len, acc, slots, tick, slab, slot_off});
   ZK_LAUNCH_CHECK();
   return 0;

@@ -50,7 +50,24 @@
 //            entry is no candidate walked, tiles covered whole by one frame
 //            filled in one step; then the counts are scanned up to the first
 //            terminal: row bases and result[0..3].
+//            The last block also scatters the frame-block index (for every
+//            256 rows, the count block their first row lies in).
 //  fs_rows   one wave per tile writes its (body offset, length) rows.
+//
+// Who writes the rows and clears the flags (zk_frame_rows.h holds the one
+// implementation of both):
+//  * plain scan: fs_rows writes foff / flen, clears every tile's candidate
+//    flags and fs_link's tail words; the next scan of the workspace may run
+//    with clean = 1.
+//  * rows deferred (flags bit 24, FS_DEFER): fs_tile and fs_link only;
+//    result[0..3] are complete, foff / flen untouched.  The table's first
+//    reader — decode_replies_tiles_k, tree_serve_tiles_k — takes each
+//    workgroup's 256 rows from the tile lists through the index, stores
+//    them to foff / flen, and clears the flags (a strided share of the tiles
+//    a workgroup, the tail words by workgroup 0).  Only after such a
+//    consumer ran may the next scan pass clean = 1; without one it memsets.
+//  * a stream of one tile at most: fs_small writes the rows; there are no
+//    flags, and no deferred mode.
 //
 // The stream length is read ON THE DEVICE (n = min(*n_dev, n_cap), e.g. an
 // encoder's total): the grids cover the buffer capacity, tiles past the
@@ -69,12 +86,10 @@
 // stalled on HBM latency at every chunk (~1 us per reply frame).  Staging
 // a 4 KiB tile once per wave removes both.
 #include "zk_common.h"
+#include "zk_frame_rows.h"   // tile constants, LW_* words, the rows
 
 namespace zk {
 
-constexpr int FT_S = 4096;                 // tile bytes
-constexpr int FT_LMAX = FT_S / 4;          // most frame starts a tile holds
-constexpr int FT_STAGE = FT_S + 16;        // staged bytes (+ length overhang)
 constexpr int64_t TERM = (int64_t)1 << 62;
 constexpr int64_t TBAD = (int64_t)1 << 60;
 constexpr int64_t FC_MAXP = (int64_t)1 << 24;
@@ -83,26 +98,12 @@ constexpr int FC_WIN = 4096;               // fs_link's staged walk window
 // inlined together spilled to scratch, 0.64 us a looked-up tile)
 constexpr int FL_T = 512;
 constexpr int FL_U = 8;                    // fs_link loads per batch
-// fs_link's grid words (see fl_check's caller)
-constexpr int FL_NB = 2;                   // broken links the check saw
-constexpr int FL_GW = FL_NB + 1;
 constexpr int FL_BROUNDS = 8;             // the last block's repair rounds
 constexpr int FL_DBG_BLOCKS = 16;          // fs_link blocks with a debug clock
 constexpr int FL_DBG_ROWS = 6;             // fs_link's debug rows past the tiles
 // The last block's one exact chase before its rounds (many broken links):
 // tiles it may walk before it leaves the rest to the rounds
 constexpr uint32_t FL_CHASE_WALKS = 16;
-// Count blocks: frame counts scanned per FK_T tiles (one wave's worth)
-constexpr int FK_T = 64;
-// The workspace's words after the X flags (uint64, lbw + 2 * tiles): [0..3]
-// stats, [4..5] the check's minima, [6] the last live tile, [7] this scan's
-// tiles without a speculated entry (fs_tile counts, fs_rows clears),
-// [8, 8 + FL_GW) fs_link's grid words, [16, 32) its barrier words (the big
-// repair, see fs_link)
-constexpr int LW_MINS = 4, LW_LAST = 6, LW_NOSPEC = 7, LW_GRID = 8;
-constexpr int LW_BIG = 16;
-constexpr int LW_END = 32;
-static_assert(LW_GRID + FL_GW <= LW_BIG, "grid words");
 // The big repair (barrier rounds over the grid) when a scan has more tiles
 // without a speculated entry than this
 constexpr unsigned FL_BIG_NOSPEC = 256;
@@ -111,14 +112,6 @@ constexpr int FL_GROUNDS = 6;              // its grid rounds
 // waits are tens of microseconds; past the bound the tile takes no
 // speculated entry and fs_link re-walks it from the exact one.
 constexpr uint64_t FT_WAIT_TICKS = 200000;
-
-// The scanned length: a producer's device-side byte count clamped to the
-// buffer capacity (null: the capacity itself, a host-known length).
-ZK_DEV int64_t stream_len(const int64_t* n_dev, int64_t n_cap) {
-  if (n_dev == nullptr) return n_cap;
-  const int64_t v = *n_dev;
-  return v < 0 ? 0 : (v < n_cap ? v : n_cap);
-}
 
 ZK_DEV uint64_t lb_load(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -141,14 +134,6 @@ ZK_DEV void fc_stat(uint64_t* stats, int k, uint32_t v) {
                          __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Big-endian i32 at byte p of an LDS image (two aligned dwords + alignbyte).
-ZK_DEV int32_t lds_be32(const uint8_t* sb, int32_t p) {
-  const int32_t a = p & ~3;
-  const uint32_t lo = *(const uint32_t*)(sb + a);
-  const uint32_t hi = *(const uint32_t*)(sb + a + 4);
-  return (int32_t)bswap32(__builtin_amdgcn_alignbyte(hi, lo, p & 3));
-}
-
 // ---- per-tile records shared with fs_link / fs_rows ------------------------
 constexpr int FT_BITS = FT_S / 32;         // uint32 words per position map
 constexpr int FT_XW = 2048 / 32;           // exit candidates: the next tile's
@@ -168,15 +153,7 @@ ZK_DEV int64_t fc_meta(const FcWalk& w) {
   return (int64_t)w.cnt | ((int64_t)w.np << 11) | ((int64_t)(w.js + 1) << 22) |
          ((int64_t)w.term << 33) | ((int64_t)w.bad << 34);
 }
-ZK_DEV int32_t m_cnt(int64_t m) { return (int32_t)(m & 0x7FF); }
-ZK_DEV int32_t m_np(int64_t m) { return (int32_t)((m >> 11) & 0x7FF); }
-ZK_DEV int32_t m_js(int64_t m) { return (int32_t)((m >> 22) & 0x7FF) - 1; }
-ZK_DEV bool m_term(int64_t m) { return (m >> 33) & 1; }
-ZK_DEV bool m_bad(int64_t m) { return (m >> 34) & 1; }
-// a tile whose exact entry, exit and frame count fs_link's chase looked up:
-// its recorded frame starts are still the old entry's, so fs_rows walks it
-constexpr int64_t M_STALE = (int64_t)1 << 35;
-ZK_DEV bool m_stale(int64_t m) { return (m >> 35) & 1; }
+// (the m_* readers and M_STALE: zk_frame_rows.h)
 
 // Resolve the survivor's end code `send` into the walk result's exit.
 ZK_DEV void fc_join_end(FcWalk& r, int64_t send, int64_t n) {
@@ -1683,31 +1660,6 @@ __global__ __launch_bounds__(256) void fs_tile(
 
 // ---- fs_link ---------------------------------------------------------------
 
-// Stage [wb, wb + WIN) (zero past n) into the wave's window: all WIN/1024
-// 16-byte loads of a lane issued before the first LDS write.
-template <int WIN>
-ZK_DEV void fc_stage(const uint8_t* __restrict__ buf, int64_t n, int64_t wb,
-                     uint8_t* win, int lane) {
-  constexpr int PER = WIN / 1024;
-  uint4 v[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const int64_t g = wb + 16 * (lane + 64 * j);
-    v[j] = make_uint4(0, 0, 0, 0);
-    if (g + 16 <= n) {
-      __builtin_memcpy(&v[j], buf + g, 16);
-    } else if (g < n) {
-      uint8_t* b = (uint8_t*)&v[j];
-      for (int k = 0; k < 16; ++k) b[k] = g + k < n ? buf[g + k] : 0;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < PER; ++j) *(uint4*)(win + 16 * (lane + 64 * j)) = v[j];
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // fs_tile's join walk from global memory (a repair from the exact entry E),
 // through a WIN-byte LDS window (4 KiB per wave: a tile in one staging).
 template <int WIN = FC_WIN>
@@ -2050,11 +2002,14 @@ ZK_DEV void fl_check(int64_t ntiles, const int64_t* __restrict__ rec_entry,
 // Row bases once every link up to the first terminal ft (INF: none) holds:
 // bsum[b] (block b's count total, the check's or re-counted) becomes block
 // b's exclusive offset; base[k] stays the in-block one; result[0..3] and
-// the last tile.  fs_link's last block alone.
+// the last tile; and the frame-block index (ZkFrameTiles.fblk: a scatter of
+// frames / 256 words, each block's thread writing those of its own rows).
+// fs_link's last block alone.
 ZK_DEV void fl_bases(int64_t n, int64_t ntiles, int64_t ft,
                      const int64_t* rec_exit, const int64_t* rec_meta,
                      const int64_t* base, int64_t* bsum, int64_t cap,
-                     int64_t* result, int64_t* lastk, int64_t* red) {
+                     int64_t* result, int64_t* lastk, int64_t* red,
+                     int32_t* fblk) {
   const int tid = threadIdx.x;
   const int64_t INF = INT64_MAX;
   const int64_t last = ft == INF ? ntiles - 1 : ft;
@@ -2070,10 +2025,12 @@ ZK_DEV void fl_bases(int64_t n, int64_t ntiles, int64_t ft,
   for (int64_t b = b0; b < b1; ++b) {
     const int64_t v = ld_agent(&bsum[b]);
     bsum[b] = run;
+    int64_t live = v;                       // the block's rows
     if (b == blast) {
       // frames up to `last` (tiles after it in its block are dead)
       const int64_t ml = ld_agent(&rec_meta[last]);
       const int64_t total = run + ld_agent(&base[last]) + m_cnt(ml);
+      live = total - run;
       *lastk = last;
       result[0] = total;
       result[3] = total > cap ? 1 : 0;
@@ -2085,6 +2042,8 @@ ZK_DEV void fl_bases(int64_t n, int64_t ntiles, int64_t ft,
         result[2] = m_bad(ml) ? 1 : 0;
       }
     }
+    for (int64_t j = (run + FR_T - 1) / FR_T; j * FR_T < run + live; ++j)
+      fblk[j] = (int32_t)b;
     run += v;
   }
 }
@@ -2504,11 +2463,13 @@ ZK_DEV void fl_chase_recount(int64_t ntiles, const int64_t* rec_meta,
 // Every live link holds up to the first terminal ft (INF: none): the
 // exclusive scan of the counts of tiles 0..ft as absolute row bases (bsum
 // zero: fs_rows adds no block offset), tiles after ft dead; result[0..3]
-// and the last tile.  The last block alone, after a repair.
+// the last tile and the frame-block index (as fl_bases).  The last block
+// alone, after a repair.
 ZK_DEV void fl_count_scan(int64_t n, int64_t ntiles, int64_t ft,
                           const int64_t* rec_exit, const int64_t* rec_meta,
                           int64_t* base, int64_t* bsum, int64_t cap,
-                          int64_t* result, int64_t* lastk, int64_t* red) {
+                          int64_t* result, int64_t* lastk, int64_t* red,
+                          int32_t* fblk) {
   const int tid = threadIdx.x;
   const int64_t INF = INT64_MAX;
   const int64_t last = ft == INF ? ntiles - 1 : ft;
@@ -2534,7 +2495,10 @@ ZK_DEV void fl_count_scan(int64_t n, int64_t ntiles, int64_t ft,
 #pragma unroll
     for (int u = 0; u < FL_U; ++u) {
       if (kb + u < k1) base[kb + u] = run;
-      run += m_cnt(v[u]);
+      const int64_t end = run + m_cnt(v[u]);
+      for (int64_t j = (run + FR_T - 1) / FR_T; j * FR_T < end; ++j)
+        fblk[j] = (int32_t)((kb + u) / FK_T);
+      run = end;
     }
   }
   for (int64_t k = last + 1 + tid; k < ntiles; k += FL_T) base[k] = -1;
@@ -2683,7 +2647,7 @@ __global__ __launch_bounds__(FL_T) void fs_link(
     int64_t* __restrict__ bsum, uint64_t* mins,
     int64_t* __restrict__ lastk, unsigned long long* g,
     const uint64_t* lbw, const int64_t* __restrict__ cx,
-    int64_t* __restrict__ ldbg) {
+    int64_t* __restrict__ ldbg, int32_t* __restrict__ fblk) {
   __shared__ __attribute__((aligned(16)))
       uint8_t win[(FL_T / 64) * (FC_WIN + 16)];      // one per wave
   __shared__ int64_t red[2 * (FL_T / 64) + 2];
@@ -2764,7 +2728,7 @@ __global__ __launch_bounds__(FL_T) void fs_link(
     // block offsets + the check's in-block bases
     if (ldbg != nullptr && tid == 0) ldbg[40] = wall_clock64();
     fl_bases(n, ntiles, ft0, rec_exit, rec_meta, base, bsum, cap, result,
-             lastk, red);
+             lastk, red, fblk);
     if (ldbg != nullptr && tid == 0) ldbg[41] = wall_clock64();
     return;
   }
@@ -2819,7 +2783,7 @@ __global__ __launch_bounds__(FL_T) void fs_link(
                           fbv, ftv);
       if (fbv == INF || fbv > ftv) {
         fl_count_scan(n, ntiles, ftv, rec_exit, rec_meta, base, bsum, cap,
-                      result, lastk, red);
+                      result, lastk, red, fblk);
         if (clk) ldbg[4] = wall_clock64() | (2ll << 56);
         return;
       }
@@ -2839,13 +2803,13 @@ __global__ __launch_bounds__(FL_T) void fs_link(
         if (changed) {
           // (tiles re-walked in rounds are not in the chases' dirty set)
           fl_count_scan(n, ntiles, ftv, rec_exit, rec_meta, base, bsum, cap,
-                        result, lastk, red);
+                        result, lastk, red, fblk);
           if (clk) ldbg[4] = wall_clock64() | (2ll << 56);
           return;
         }
         fl_chase_recount(ntiles, rec_meta, base, bsum, ch);
         fl_bases(n, ntiles, ftv, rec_exit, rec_meta, base, bsum, cap, result,
-                 lastk, red);
+                 lastk, red, fblk);
         if (clk) ldbg[4] = wall_clock64() | (1ll << 56);
         return;
       }
@@ -2896,7 +2860,7 @@ __global__ __launch_bounds__(FL_T) void fs_link(
     }
   }
   fl_count_scan(n, ntiles, ft, rec_exit, rec_meta, base, bsum, cap, result,
-                lastk, red);
+                lastk, red, fblk);
   if (clk) ldbg[4] = wall_clock64() | (3ll << 56);
 }
 
@@ -2945,57 +2909,25 @@ __global__ __launch_bounds__(256) void fs_rows(
   const int64_t b = bsum[t / FK_T] + base[t];
   const int64_t m = rec_meta[t];
   const int64_t x = rec_exit[t];
-  const int32_t cnt = m_cnt(m), np = m_np(m), js = m_js(m);
-  const int64_t ts = t * FT_S;
-  const uint16_t* P = pre + t * FT_LMAX;
-  const uint16_t* R = list + t * FT_LMAX + (js < 0 ? 0 : js);
-  if (m_stale(m)) {
-    uint8_t* sb = stage[wv];
-    fc_stage<FT_S>(buf, n, ts, sb, lane);
-    if (lane == 0) {
-      uint8_t* pb = sb + FT_S;
-      for (int k = 0; k < 16; ++k)
-        pb[k] = ts + FT_S + k < n ? buf[ts + FT_S + k] : 0;
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // the walk keeps 64 starts in the lanes (lane k & 63 holds start k)
-    // and writes their rows every 64 frames
-    int32_t c = __builtin_amdgcn_readfirstlane((int32_t)(rec_entry[t] - ts));
-    int32_t ent = 0;
-    for (int32_t k = 0; k < cnt; ++k) {
-      ent = lane == (k & 63) ? c : ent;
-      const int32_t len = __builtin_amdgcn_readfirstlane(lds_be32(sb, c));
-      c += 4 + len;
-      if ((k & 63) == 63 || k == cnt - 1) {
-        const int32_t last = k & 63;
-        const int32_t nxt = __shfl_down(ent, 1, 64);
-        if (lane <= last) {
-          const int64_t p = ts + ent;
-          const int64_t q = lane < last ? ts + nxt
-                                        : (k == cnt - 1 ? x : ts + c);
-          const int64_t idx = b + (k & ~63) + lane;
-          if (idx < cap) {
-            foff[idx] = p + 4;
-            flen[idx] = (int32_t)(q - p - 4);
-          }
-        }
-      }
-    }
-    return;
-  }
-  // a frame ends where the next one of the chain starts, the tile's last
-  // at the tile's exit (the next tile's first frame, or the stop offset of
-  // a terminal tile): lengths come from the recorded starts, no stream read
-  for (int32_t k = lane; k < cnt; k += 64) {
-    const int64_t p = ts + (k < np ? P[k] : R[k - np]);
-    const int32_t k1 = k + 1;
-    const int64_t q = k1 < cnt ? ts + (k1 < np ? P[k1] : R[k1 - np]) : x;
+  const int32_t cnt = m_cnt(m);
+  auto row = [&](int32_t k, int64_t p, int64_t q) {
     const int64_t idx = b + k;
     if (idx < cap) {
       foff[idx] = p + 4;
       flen[idx] = (int32_t)(q - p - 4);
     }
+  };
+  if (m_stale(m)) {
+    const int32_t c = __builtin_amdgcn_readfirstlane(
+        (int32_t)(rec_entry[t] - t * FT_S));
+    fr_walk_stale<false>(buf, n, t, c, cnt, x, stage[wv], lane, row);
+    return;
+  }
+  // lengths come from the recorded starts, no stream read (zk_frame_rows.h)
+  for (int32_t k = lane; k < cnt; k += 64) {
+    int64_t p, q;
+    fr_bounds(list, pre, t, m, x, k, p, q);
+    row(k, p, q);
   }
 }
 
@@ -3036,7 +2968,7 @@ __global__ __launch_bounds__(64) void fs_small(
 struct FsPlan {
   int64_t tiles;
   size_t off_list, off_pre, off_sx, off_lbw, off_rent, off_rexit, off_rmeta,
-      off_rcnt, off_base, off_blist, off_bsum, off_cx, total;
+      off_rcnt, off_base, off_blist, off_bsum, off_cx, off_fblk, total;
 };
 
 static FsPlan fs_plan(int64_t n) {
@@ -3058,6 +2990,8 @@ static FsPlan fs_plan(int64_t n) {
   p.off_blist = take((size_t)tiles * 4);
   p.off_bsum = take((size_t)(tiles / FK_T + 1) * 8);
   p.off_cx = take((size_t)tiles * 5 * 8);   // candidate exits (fs_tile)
+  // the frame-block index: a tile holds at most FT_LMAX frames
+  p.off_fblk = take((size_t)(tiles * (FT_LMAX / FR_T) + 1) * 4);
   p.total = o;
   return p;
 }
@@ -3073,6 +3007,10 @@ static int32_t fs_minb() { return 8; }
 // scan flag: frames may be longer than the window (fs_tile's frontier
 // passes past the window, and survivor exits past it as candidates)
 constexpr int32_t FS_LONG = 2;
+// scan flag: rows deferred — no fs_rows launch; a consumer that reads the
+// tile lists (zk_frame_tiles, zk_frame_rows.h) writes the rows and clears
+// the flags.  Not for streams of one tile at most (fs_small has no lists).
+constexpr int32_t FS_DEFER = 1 << 24;
 
 // `window` values with this bit: FS_LONG (zkmi.ops.batch.frame_window sets
 // it when the window is below the stream's largest frame)
@@ -3152,11 +3090,16 @@ int zk_frame_scan(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
                   int32_t clean, int32_t flags, hipStream_t st) {
   using namespace zk;
   const int W = fs_window(window);
+  const bool defer = (flags & FS_DEFER) != 0;
+  flags &= ~FS_DEFER;
   if (window & FS_WIN_LONG) flags |= FS_LONG;
   if (maxp > FC_MAXP || maxp < 0) return -3;
   FsPlan p = fs_plan(n_cap);
   if ((int64_t)p.total > ws_bytes) return -1;
   const int64_t tiles = p.tiles;
+  // (no tile lists a consumer could take for a stream of one tile at most:
+  // zk_frame_tiles refuses it, whichever path the scan itself would take)
+  if (defer && n_cap <= FT_S) return -5;
   if (n_cap <= FT_S && !(flags & (1 | 0xFFFF00)) &&
       fs_dbg_buf(tiles) == nullptr) {
     fs_small<<<1, 64, 0, st>>>(buf, n_dev, n_cap, maxp, foff, flen, cap,
@@ -3176,6 +3119,7 @@ int zk_frame_scan(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
   int32_t* blist = (int32_t*)(ws + p.off_blist);
   int64_t* bsum = (int64_t*)(ws + p.off_bsum);
   int64_t* cx = (int64_t*)(ws + p.off_cx);
+  int32_t* fblk = (int32_t*)(ws + p.off_fblk);
   uint64_t* mins = lbw + 2 * tiles + LW_MINS;
   int64_t* lastk = (int64_t*)(lbw + 2 * tiles + LW_LAST);
   unsigned long long* grid = (unsigned long long*)(lbw + 2 * tiles + LW_GRID);
@@ -3233,12 +3177,40 @@ int zk_frame_scan(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
   fs_link<<<fl_blocks(), FL_T, 0, st>>>(buf, n_dev, n_cap, maxp, sx, list, rcnt,
                                  pre, rent, rexit, rmeta, base, cap, result,
                                  lbw + 2 * tiles, blist, bsum, mins, lastk,
-                                 grid, lbw, cx, dbg ? dbg + 8 * tiles : nullptr);
+                                 grid, lbw, cx, dbg ? dbg + 8 * tiles : nullptr,
+                                 fblk);
   ZK_LAUNCH_CHECK();
+  if (defer) return 0;
   fs_rows<<<(unsigned)((tiles + 3) / 4), 256, 0, st>>>(
       buf, n_dev, n_cap, list, pre, rmeta, rent, rexit, base, bsum, lastk,
       foff, flen, cap, lbw, lbw + 2 * tiles);
   ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+// The tile lists of a (rows-deferred) scan over n_cap bytes on workspace ws,
+// for the consumers' launchers.
+int zk_frame_tiles(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
+                   uint8_t* ws, int64_t ws_bytes, ZkFrameTiles* out) {
+  using namespace zk;
+  if (n_cap <= FT_S) return -2;
+  FsPlan p = fs_plan(n_cap);
+  if ((int64_t)p.total > ws_bytes) return -1;
+  uint64_t* lbw = (uint64_t*)(ws + p.off_lbw);
+  out->buf = buf;
+  out->n_dev = n_dev;
+  out->n_cap = n_cap;
+  out->list = (const uint16_t*)(ws + p.off_list);
+  out->pre = (const uint16_t*)(ws + p.off_pre);
+  out->rec_meta = (const int64_t*)(ws + p.off_rmeta);
+  out->rec_entry = (const int64_t*)(ws + p.off_rent);
+  out->rec_exit = (const int64_t*)(ws + p.off_rexit);
+  out->base = (const int64_t*)(ws + p.off_base);
+  out->bsum = (const int64_t*)(ws + p.off_bsum);
+  out->lastk = (const int64_t*)(lbw + 2 * p.tiles + LW_LAST);
+  out->fblk = (const int32_t*)(ws + p.off_fblk);
+  out->lbw = lbw;
+  out->tiles = p.tiles;
   return 0;
 }
 

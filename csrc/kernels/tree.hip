@@ -6,6 +6,7 @@
 // (SEQUENTIAL numbering), tree_list.hip (GET_CHILDREN*), tree_watch.hip
 // (watch events and the SET_WATCHES catch-up).
 #include "zk_tree.h"
+#include "zk_frame_rows.h"
 
 namespace zk {
 
@@ -283,9 +284,15 @@ ZK_DEV int32_t do_create(const ZkTree& t, Lane& L, const uint8_t* data,
 // block-wide ticket barriers per workgroup; any other op is answered
 // UNIMPLEMENTED.  (A run-time vote of the block for the same skip cost the
 // create storm 10 %; a template costs the write batches nothing.)
-template <bool PARSE, bool RO = false>
-__global__ __launch_bounds__(TR_T) void tree_serve_k(
-    ZkTree t, const uint8_t* __restrict__ rx, ZkReqOut q,
+// TILES (with PARSE): after a rows-deferred K1 scan of the request stream.
+// The frame's row comes from the scan's tile lists T (zk_frame_rows.h)
+// instead of the table; the workgroup also writes its rows to the table
+// (rows_off / rows_len, what fs_rows would have written) and clears its
+// share of the scan's flags.
+static_assert(TR_T == FR_T, "a workgroup per block of FR_T frames");
+template <bool PARSE, bool RO, bool TILES>
+ZK_DEV void tree_serve_body(
+    const ZkTree& t, const uint8_t* __restrict__ rx, const ZkReqOut& q,
     const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
     const int64_t* __restrict__ n_dev, int64_t ncap, int32_t* __restrict__ r_op,
     int32_t* __restrict__ r_xid, int32_t* __restrict__ r_err,
@@ -295,11 +302,23 @@ __global__ __launch_bounds__(TR_T) void tree_serve_k(
     int64_t* __restrict__ r_bsum, int64_t session, int64_t now_ms,
     const uint8_t* __restrict__ rank, int32_t pass, int32_t last_pass,
     int64_t snap_base, int64_t snap_cap, int64_t* __restrict__ snap_top,
-    int32_t wslot, int64_t* __restrict__ fired) {
+    int32_t wslot, int64_t* __restrict__ fired, const ZkFrameTiles* T,
+    int64_t* __restrict__ rows_off, int32_t* __restrict__ rows_len) {
   session = sess_of(t, session);
   const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);
   const int64_t i = (int64_t)blk * TR_T + threadIdx.x;
   const bool in_batch = i < ncap && i < *n_dev;
+  int64_t fo = 0;                    // the frame's row (TILES)
+  int32_t fl = 0;
+  if (TILES) {
+    __shared__ FrLds rows;
+    const int64_t nf = *n_dev;
+    if (fr_row(*T, blk, nf < ncap ? nf : ncap, rows, fo, fl)) {
+      rows_off[i] = fo;
+      rows_len[i] = fl;
+    }
+    fr_housekeep(*T);
+  }
   // ordered passes: this launch serves the requests of rank `pass`; the
   // last pass also answers any of a higher rank, refused (SYSTEMERROR: more
   // same-path requests than passes).  rank bit 7: a later request of the
@@ -311,7 +330,8 @@ __global__ __launch_bounds__(TR_T) void tree_serve_k(
   ReqFields rq{ST_BAD_DECODE, 0, OP_PING, 0, 0, 0, 0, -1, -1, -1, 0};
   if (live) {
     if (PARSE) {
-      rq = parse_request(rx, foff[i], flen[i]);
+      rq = TILES ? parse_request(rx, fo, fl)
+                 : parse_request(rx, foff[i], flen[i]);
     } else {
       rq.status = q.status[i];
       rq.xid = q.xid[i];
@@ -576,12 +596,59 @@ __global__ __launch_bounds__(TR_T) void tree_serve_k(
   if (r_slot != nullptr) r_slot[i] = L.op == OP_DELETE ? -1 : L.slot;
 }
 
+template <bool PARSE, bool RO = false>
+__global__ __launch_bounds__(TR_T) void tree_serve_k(
+    ZkTree t, const uint8_t* __restrict__ rx, ZkReqOut q,
+    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
+    const int64_t* __restrict__ n_dev, int64_t ncap, int32_t* __restrict__ r_op,
+    int32_t* __restrict__ r_xid, int32_t* __restrict__ r_err,
+    int64_t* __restrict__ r_node, int64_t* __restrict__ r_zxid,
+    int64_t* __restrict__ r_path_off, int32_t* __restrict__ r_path_len,
+    int64_t* __restrict__ r_slot, int64_t* __restrict__ r_sizes,
+    int64_t* __restrict__ r_bsum, int64_t session, int64_t now_ms,
+    const uint8_t* __restrict__ rank, int32_t pass, int32_t last_pass,
+    int64_t snap_base, int64_t snap_cap, int64_t* __restrict__ snap_top,
+    int32_t wslot, int64_t* __restrict__ fired) {
+  tree_serve_body<PARSE, RO, false>(
+      t, rx, q, foff, flen, n_dev, ncap, r_op, r_xid, r_err, r_node, r_zxid,
+      r_path_off, r_path_len, r_slot, r_sizes, r_bsum, session, now_ms, rank,
+      pass, last_pass, snap_base, snap_cap, snap_top, wslot, fired, nullptr,
+      nullptr, nullptr);
+}
+
+// The parsing serve over a rows-deferred scan's tile lists (one pass: no
+// ranks, no snapshots).
+template <bool RO>
+__global__ __launch_bounds__(TR_T) void tree_serve_tiles_k(
+    ZkTree t, ZkFrameTiles T, int64_t* __restrict__ rows_off,
+    int32_t* __restrict__ rows_len, const int64_t* __restrict__ n_dev,
+    int64_t ncap, ZkServeOut o, int64_t session, int64_t now_ms,
+    int32_t wslot, int64_t* __restrict__ fired) {
+  tree_serve_body<true, RO, true>(
+      t, T.buf, ZkReqOut{}, nullptr, nullptr, n_dev, ncap, o.opcode, o.xid,
+      o.err, o.node, o.zxid, o.path_off, o.path_len, o.slot, o.sizes,
+      o.block_sums, session, now_ms, nullptr, 0, 1, 0, 0, nullptr, wslot,
+      fired, &T, rows_off, rows_len);
+}
+
 // The one launch site of tree_serve_k (zk_tree.h ServeLaunch): its
-// <false, false>, <true, false> and <true, true> instances.
+// <false, false>, <true, false> and <true, true> instances, and the two of
+// tree_serve_tiles_k.
 int serve_launch(const ServeLaunch& s, hipStream_t st) {
   if (s.ncap <= 0) return 0;
   const ZkServeOut& o = *s.out;
   if ((o.sizes == nullptr) != (o.block_sums == nullptr)) return -1;
+  if (s.tiles != nullptr) {
+    // after a rows-deferred scan: the frame table receives the rows
+    if (s.q != nullptr || s.rank != nullptr) return -1;
+    const auto kt = s.read_only ? tree_serve_tiles_k<true>
+                                : tree_serve_tiles_k<false>;
+    kt<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T, 0, st>>>(
+        *s.tree, *s.tiles, s.rows_off, s.rows_len, s.n_dev, s.ncap, o,
+        s.session, s.now_ms, s.wslot, s.fired);
+    ZK_LAUNCH_CHECK();
+    return 0;
+  }
   const bool parse = s.q == nullptr;
   const auto k = !parse        ? tree_serve_k<false>
                  : s.read_only ? tree_serve_k<true, true>
@@ -629,6 +696,23 @@ int zk_tree_serve_frames(const ZkTree* t, const uint8_t* rx,
   s.tree = t, s.rx = rx, s.foff = foff, s.flen = flen, s.n_dev = n_dev;
   s.ncap = ncap, s.out = out, s.session = session, s.now_ms = now_ms;
   s.wslot = wslot, s.fired = fired, s.read_only = read_only;
+  return zk::serve_launch(s, st);
+}
+
+// zk_tree_serve_frames after a rows-deferred scan of the request stream
+// (zk_frame_scan flags bit 24): the rows come from the scan's tile lists;
+// foff / flen [ncap] receive them and the scan's workspace is left clean.
+int zk_tree_serve_tiles(const ZkTree* t, const ZkFrameTiles* tiles,
+                        int64_t* foff, int32_t* flen, const int64_t* n_dev,
+                        int64_t ncap, const ZkServeOut* out, int64_t session,
+                        int64_t now_ms, int32_t wslot, int64_t* fired,
+                        int32_t read_only, hipStream_t st) {
+  if (ncap <= 0) return (int)hipErrorInvalidValue;  // (the flags stay set)
+  zk::ServeLaunch s;
+  s.tree = t, s.rx = tiles->buf, s.tiles = tiles, s.rows_off = foff;
+  s.rows_len = flen, s.n_dev = n_dev, s.ncap = ncap, s.out = out;
+  s.session = session, s.now_ms = now_ms, s.wslot = wslot, s.fired = fired;
+  s.read_only = read_only;
   return zk::serve_launch(s, st);
 }
 

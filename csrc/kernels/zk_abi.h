@@ -177,6 +177,30 @@ struct ZkAclTable {
   int64_t* ctr;
 };
 
+// K1's per-tile frame-start lists, as a consumer of a rows-deferred scan
+// (zk_frame_scan flags bit 24) reads them: zk_frame_rows.h turns a
+// workgroup's 256 frames into (body offset, length) rows from these, and
+// clears the scan's flag words for the next scan of the workspace.
+// zk_frame_tiles fills it from the workspace a scan ran on.
+struct ZkFrameTiles {
+  const uint8_t* buf;        // the stream
+  const int64_t* n_dev;      // its device length (null: n_cap)
+  int64_t n_cap;
+  const uint16_t* list;      // [tiles][1024] frame starts of the tile's chain
+  const uint16_t* pre;       // [tiles][1024] starts walked before joining it
+  const int64_t* rec_meta;   // [tiles] cnt | np | js | term | bad | stale
+  const int64_t* rec_entry;  // [tiles]
+  const int64_t* rec_exit;   // [tiles]
+  const int64_t* base;       // [tiles] row base within the tile's count block
+  const int64_t* bsum;       // [tiles / 64 + 1] row base of the count block
+  const int64_t* lastk;      // [1] the last live tile (-1: no frame)
+  // [4 * tiles + 1] per block of 256 frames: the count block (64 tiles)
+  // holding the tile in which frame 256 j starts (fs_link's last workgroup)
+  const int32_t* fblk;
+  uint64_t* lbw;             // flag words: two a tile, then the LW_* tail
+  int64_t tiles;             // of the workspace's layout (n_cap's)
+};
+
 // ---- launchers (stream-ordered; return 0 or a hipError_t) ----------------
 int64_t zk_scan_workspace(int64_t n);
 int zk_scan_set_mode(int mode);
@@ -213,6 +237,22 @@ int zk_frame_scan(const uint8_t*, const int64_t*, int64_t, int64_t,
 int zk_frame_scan_stats(const uint8_t*, int64_t, int32_t, uint32_t*,
                         hipStream_t);
 int zk_frame_scan_dbg(int64_t* host, int64_t tiles);
+// the tile lists of the scan of buf[0, min(*n_dev, n_cap)) on workspace ws
+// (-1: workspace too small; -2: a stream of one tile at most has none)
+int zk_frame_tiles(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
+                   uint8_t* ws, int64_t ws_bytes, ZkFrameTiles* out);
+// zk_decode_replies / _check after a rows-deferred scan: the rows come from
+// the tile lists and are also written to foff / flen [ncap]
+int zk_decode_replies_tiles(const ZkFrameTiles*, int64_t*, int32_t*,
+                            const int64_t*, int64_t, const int64_t*, int64_t,
+                            const ZkReplyOut*, hipStream_t);
+int zk_decode_replies_check_tiles(const ZkFrameTiles*, int64_t*, int32_t*,
+                                  const int64_t*, int64_t, const int64_t*,
+                                  int64_t, const ZkReplyOut*, const int64_t*,
+                                  const int32_t*, const int32_t*,
+                                  unsigned long long*, int32_t, int64_t*,
+                                  const uint8_t*, const int64_t*,
+                                  hipStream_t);
 int zk_decode_replies(const uint8_t*, const int64_t*, const int32_t*,
                       const int64_t*, int64_t, const int64_t*, int64_t,
                       const ZkReplyOut*, hipStream_t);
@@ -250,6 +290,11 @@ int zk_tree_serve_frames(const ZkTree*, const uint8_t*, const int64_t*,
                          const int32_t*, const int64_t*, int64_t,
                          const ZkServeOut*, int64_t, int64_t, int32_t,
                          int64_t*, int32_t, hipStream_t);
+// zk_tree_serve_frames after a rows-deferred scan of the request stream
+int zk_tree_serve_tiles(const ZkTree*, const ZkFrameTiles*, int64_t*,
+                        int32_t*, const int64_t*, int64_t, const ZkServeOut*,
+                        int64_t, int64_t, int32_t, int64_t*, int32_t,
+                        hipStream_t);
 int zk_tree_finish_scan(const ZkTree*, const int64_t*, int64_t, int32_t,
                         int64_t, int64_t*, int64_t*, hipStream_t);
 int zk_tree_serve_ordered(const ZkTree*, const uint8_t*, const ZkReqOut*,
@@ -370,6 +415,8 @@ static_assert(sizeof(ZkAclTable) == 8 * 8, "ZkAclTable layout");
 static_assert(offsetof(ZkAclTable, arena) == 2 * 8, "ZkAclTable.arena");
 static_assert(offsetof(ZkAclTable, hmask) == 6 * 8, "ZkAclTable.hmask");
 static_assert(sizeof(ZkTree) == 27 * 8, "ZkTree layout");
+static_assert(sizeof(ZkFrameTiles) == 14 * 8, "ZkFrameTiles layout");
+static_assert(offsetof(ZkFrameTiles, fblk) == 11 * 8, "ZkFrameTiles.fblk");
 static_assert(offsetof(ZkTree, store) == 9 * 8, "ZkTree.store");
 static_assert(offsetof(ZkTree, free_list) == 14 * 8, "ZkTree.free_list");
 static_assert(offsetof(ZkTree, wt_hmask) == 25 * 8, "ZkTree.wt_hmask");

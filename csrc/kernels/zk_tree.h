@@ -755,6 +755,11 @@ struct ServeLaunch {
   int32_t wslot = -1;
   int64_t* fired = nullptr;
   int32_t read_only = 0;
+  // after a rows-deferred K1 scan: its tile lists, and the frame table the
+  // serve writes the rows to (foff / flen unused)
+  const ZkFrameTiles* tiles = nullptr;
+  int64_t* rows_off = nullptr;
+  int32_t* rows_len = nullptr;
 };
 int serve_launch(const ServeLaunch& s, hipStream_t st);
 

@@ -523,6 +523,81 @@ void decode_replies_check(const Tensor& buf, const Tensor& foff,
          "decode_replies_check");
 }
 
+// The tile lists of the rows-deferred scan (frame_scan flags bit 24) that
+// ran over buf[:n_cap] on workspace ws.
+ZkFrameTiles frame_tiles(const Tensor& buf, const c10::optional<Tensor>& n_dev,
+                         int64_t n_cap, const Tensor& ws) {
+  TORCH_CHECK(n_cap >= 0 && n_cap <= buf.numel(),
+              "zkmi: frame tiles: length ", n_cap, " past the buffer (",
+              buf.numel(), " bytes)");
+  ZkFrameTiles t;
+  const int rc = zk_frame_tiles(
+      P<uint8_t>(buf, U8, 1, "buf"),
+      Popt<int64_t>(n_dev, I64, 1, "n", &buf), n_cap,
+      P<uint8_t>(ws, U8, 1, "ws", &buf), ws.numel(), &t);
+  TORCH_CHECK(rc != -2, "zkmi: a stream of one tile at most has no tile "
+              "lists (its scan writes the rows itself)");
+  TORCH_CHECK(rc == 0, "zkmi: frame tiles: workspace too small");
+  return t;
+}
+
+// decode_replies / decode_replies_check after a rows-deferred scan: the rows
+// come from the scan's tile lists and are also written to foff / flen.
+void decode_replies_tiles(const Tensor& buf,
+                          const c10::optional<Tensor>& n_bytes, int64_t n_cap,
+                          const Tensor& ws, const Tensor& foff,
+                          const Tensor& flen, const Tensor& n_dev,
+                          const Tensor& xid_tab, int64_t xid_mask,
+                          const std::vector<Tensor>& out) {
+  const int64_t cap = foff.numel();
+  TORCH_CHECK(cap >= 1, "zkmi: decode_replies_tiles: an empty frame table");
+  ZkReplyOut o = reply_out(out, cap, &buf);
+  ZkFrameTiles t = frame_tiles(buf, n_bytes, n_cap, ws);
+  hip_ok(zk_decode_replies_tiles(
+             &t, P<int64_t>(foff, I64, cap, "frame_off", &buf),
+             P<int32_t>(flen, I32, cap, "frame_len", &buf),
+             P<int64_t>(n_dev, I64, 1, "count", &buf), cap,
+             P<int64_t>(xid_tab, I64, xid_mask + 1, "xid_tab", &buf),
+             xid_mask, &o, cur_stream()),
+         "decode_replies_tiles");
+}
+
+void decode_replies_check_tiles(
+    const Tensor& buf, const c10::optional<Tensor>& n_bytes, int64_t n_cap,
+    const Tensor& ws, const Tensor& foff, const Tensor& flen,
+    const Tensor& n_dev, const Tensor& xid_tab, int64_t xid_mask,
+    const std::vector<Tensor>& out, const Tensor& idx, const Tensor& xid,
+    const Tensor& data_len, const Tensor& acc,
+    const c10::optional<Tensor>& tick, const c10::optional<Tensor>& slab,
+    const c10::optional<Tensor>& slot_off) {
+  const int64_t cap = foff.numel();
+  TORCH_CHECK(cap >= 1,
+              "zkmi: decode_replies_check_tiles: an empty frame table");
+  ZkReplyOut o = reply_out(out, cap, &buf);
+  const int32_t slots = (int32_t)std::min<int64_t>(acc.numel(), 64);
+  TORCH_CHECK(slots >= 1, "zkmi: decode_replies_check needs an acc slot");
+  TORCH_CHECK(slab.has_value() == slot_off.has_value(),
+              "zkmi: decode_replies_check: slab and slot_off go together");
+  if (slot_off.has_value())
+    TORCH_CHECK(slot_off->numel() >= data_len.numel(),
+                "zkmi: decode_replies_check: slot_off shorter than data_len");
+  ZkFrameTiles t = frame_tiles(buf, n_bytes, n_cap, ws);
+  hip_ok(zk_decode_replies_check_tiles(
+             &t, P<int64_t>(foff, I64, cap, "frame_off", &buf),
+             P<int32_t>(flen, I32, cap, "frame_len", &buf),
+             P<int64_t>(n_dev, I64, 1, "count", &buf), cap,
+             P<int64_t>(xid_tab, I64, xid_mask + 1, "xid_tab", &buf),
+             xid_mask, &o, P<int64_t>(idx, I64, cap, "idx", &buf),
+             P<int32_t>(xid, I32, cap, "xid", &buf),
+             P<int32_t>(data_len, I32, 1, "data_len", &buf),
+             reinterpret_cast<unsigned long long*>(
+                 P<int64_t>(acc, I64, slots, "acc", &buf)),
+             slots, Popt<int64_t>(tick, I64, 2, "tick", &buf),
+             Popt<uint8_t>(slab, U8, 1, "slab", &buf),
+             Popt<int64_t>(slot_off, I64, 1, "slot_off", &buf), cur_stream()),
+         "decode_replies_check_tiles");
+}
+
 void expand_strings(const Tensor& buf, const Tensor& region,
                     const Tensor& count, const Tensor& base,
                     const Tensor& soff, const Tensor& slen) {
@@ -677,6 +752,35 @@ void tree_serve_frames(const std::vector<Tensor>& t, const Tensor& rx,
              now_ms, (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
              read_only ? 1 : 0, cur_stream()),
          "tree_serve_frames");
+}
+
+// tree_serve_frames after a rows-deferred scan of rx[:n_cap] on workspace
+// ws: the serve reads the scan's tile lists and writes the rows to foff /
+// flen itself.
+void tree_serve_tiles(const std::vector<Tensor>& t, const Tensor& rx,
+                      const c10::optional<Tensor>& n_bytes, int64_t n_cap,
+                      const Tensor& ws, const Tensor& foff, const Tensor& flen,
+                      const Tensor& n_dev, int64_t ncap,
+                      const std::vector<Tensor>& r, int64_t session,
+                      int64_t now_ms, int64_t wslot,
+                      const c10::optional<Tensor>& fired,
+                      const c10::optional<Tensor>& seqno, bool read_only) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  TORCH_CHECK(ncap >= 1, "zkmi: tree_serve_tiles: an empty frame table");
+  ZkServeOut ro = serve_out(r, ncap, d);
+  s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
+  TORCH_CHECK(wslot >= -1 && wslot < 64, "zkmi: watcher slot -1..63");
+  TORCH_CHECK(rx.device() == d->device(), "zkmi: rx on the tree's device");
+  ZkFrameTiles ft = frame_tiles(rx, n_bytes, n_cap, ws);
+  hip_ok(zk_tree_serve_tiles(
+             &s, &ft, P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, session,
+             now_ms, (int32_t)wslot,
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
+             read_only ? 1 : 0, cur_stream()),
+         "tree_serve_tiles");
 }
 
 int64_t tree_order_workspace(int64_t n) {
@@ -1274,6 +1378,17 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(c!)? tick=None, Tensor? slab=None, Tensor? slot_off=None) "
         "-> ()",
         &decode_replies_check);
+  m.def("decode_replies_tiles(Tensor buf, Tensor? n, int n_cap, "
+        "Tensor(a!) ws, Tensor(b!) frame_off, Tensor(c!) frame_len, "
+        "Tensor count, Tensor xid_tab, int xid_mask, Tensor(d!)[] out) -> ()",
+        &decode_replies_tiles);
+  m.def("decode_replies_check_tiles(Tensor buf, Tensor? n, int n_cap, "
+        "Tensor(a!) ws, Tensor(b!) frame_off, Tensor(c!) frame_len, "
+        "Tensor count, Tensor xid_tab, int xid_mask, Tensor(d!)[] out, "
+        "Tensor idx, Tensor xid, Tensor data_len, Tensor(e!) acc, "
+        "Tensor(f!)? tick=None, Tensor? slab=None, Tensor? slot_off=None) "
+        "-> ()",
+        &decode_replies_check_tiles);
   m.def("expand_strings(Tensor buf, Tensor region, Tensor count, "
         "Tensor base, Tensor(a!) str_off, Tensor(b!) str_len) -> ()",
         &expand_strings);
@@ -1304,6 +1419,12 @@ TORCH_LIBRARY(zkmi, m) {
         "int session, int now_ms, int wslot=-1, Tensor(c!)? fired=None, "
         "Tensor? seqno=None, bool read_only=False) -> ()",
         &tree_serve_frames);
+  m.def("tree_serve_tiles(Tensor(a!)[] tree, Tensor rx, Tensor? n, "
+        "int n_cap, Tensor(b!) ws, Tensor(c!) frame_off, "
+        "Tensor(d!) frame_len, Tensor count, int ncap, Tensor(e!)[] out, "
+        "int session, int now_ms, int wslot=-1, Tensor(f!)? fired=None, "
+        "Tensor? seqno=None, bool read_only=False) -> ()",
+        &tree_serve_tiles);
   m.def("tree_order_workspace(int n) -> int", &tree_order_workspace);
   m.def("tree_order_stats_offset(int n) -> int", &tree_order_stats_offset);
   m.def("tree_serve_ordered(Tensor(a!)[] tree, Tensor rx, Tensor[] requests, "

@@ -423,8 +423,19 @@ class GpuServer(object):
     to a :class:`GpuTree`, encode replies."""
 
     def __init__(self, tree, cap_frames, out_cap, window=2048,
-                 seq_order=True, group=_SRV_GROUP):
+                 seq_order=True, group=_SRV_GROUP, fused_rows=False):
         self.tree = tree
+        # fused_rows: :meth:`serve` scans the requests with K1's rows pass
+        # deferred and the serve kernel reads the scan's tile lists (one
+        # launch less; csrc/kernels/zk_frame_rows.h).  Only where the serve
+        # is the frame table's first reader: unordered, no SEQUENTIAL
+        # numbering, no ACL table, no watch resume.
+        if fused_rows and (tree.acl is not None or
+                           (seq_order and cap_frames <= _SEQ_MAX)):
+            raise ValueError('fused_rows: the serve must be the first '
+                             'reader of the frame table (no seq_order, no '
+                             'ACL table)')
+        self.fused_rows = fused_rows
         self.window = window              # K1 entry window of the requests
         # SEQUENTIAL creates numbered in stream order before each serve
         # (csrc/kernels/tree_seq.hip: five launches); a server whose
@@ -576,7 +587,14 @@ class GpuServer(object):
 
 """
         L = _lib.lib()
-        ft = self.scanner.scan(rx, n)
+        if self.fused_rows and (ordered or resume or self.seq_order or
+                                self.tree.acl is not None):
+            raise ValueError('fused_rows: the serve must be the first '
+                             'reader of the frame table (not ordered, no '
+                             'seq_order, no ACL table, no watch resume)')
+        ft = self.scanner.scan(rx, n, rows=not self.fused_rows)
+        # (None for a request stream of one tile at most: the plain serve)
+        tiles = self.scanner.pending
         # ordered serving ranks the batch from K12's request table; the
         # plain serve parses each frame in registers instead
         rt = B.decode_requests(rx, ft, out=self.rt) if ordered else None
@@ -598,10 +616,18 @@ class GpuServer(object):
                                  wslot, self.fired if self.tree.watch
                                  is not None else None, seqno)
         else:
-            L.tree_serve_frames(self.tree.tensors, rx, ft.off, ft.length,
-                                ft.count, self.cap_frames, out, session, now,
-                                wslot, self.fired if self.tree.watch
-                                is not None else None, seqno, self.read_only)
+            fired = self.fired if self.tree.watch is not None else None
+            if tiles is not None:
+                # the rows-deferred scan's consumer: it writes ft's rows
+                L.tree_serve_tiles(self.tree.tensors, rx, tiles.n_dev,
+                                   tiles.ncap, tiles.ws, ft.off, ft.length,
+                                   ft.count, self.cap_frames, out, session,
+                                   now, wslot, fired, seqno, self.read_only)
+                tiles.consumed()
+            else:
+                L.tree_serve_frames(self.tree.tensors, rx, ft.off, ft.length,
+                                    ft.count, self.cap_frames, out, session,
+                                    now, wslot, fired, seqno, self.read_only)
             # the finish and K13's block-sum scan: one launch
             L.tree_finish_scan(self.tree.tensors, ft.count, 0, True,
                                self.cap_frames, self.presized[1],
@@ -815,7 +841,10 @@ class GetPipeline(object):
         # K1 windows: the largest request / reply frame of this workload
         self.server = GpuServer(tree, n, n * (4 + 16 + 4 + dmax + 68) + 64,
                                 window=B.frame_window(17 + maxpath),
-                                seq_order=False, group=_GET_SRV_GROUP)
+                                seq_order=False, group=_GET_SRV_GROUP,
+                                # (a tree with an ACL table keeps the whole
+                                # step on the plain path, reply side too)
+                                fused_rows=tree.acl is None)
         self.server.read_only = True
         self.rwindow = B.frame_window(4 + 16 + 4 + dmax + 68)
         lo, hi = tree.data_dist or (tree.data_bytes, tree.data_bytes)
@@ -944,7 +973,10 @@ class GetPipeline(object):
             pass
         rx, rtotal, rerr, _ = self.server.result
         yield
-        ft = self.rscanner.scan(rx, _len(rtotal))
+        # K1 without its rows pass on both streams: the serve and the decode
+        # read the scans' tile lists (11 launches a connection, not 13)
+        ft = self.rscanner.scan(rx, _len(rtotal),
+                                rows=not self.server.fused_rows)
         if parent is not None:
             validate, acc = parent._validate, parent._acc
         # the reply check rides in the decode kernel (acc: 1..64 slots)
@@ -953,7 +985,8 @@ class GetPipeline(object):
         # the device step counter advances in the checking decode (one
         # launch less per step), else on its own
         rep = B.decode_replies(rx, ft, self.xt, out=self.reply, check=chk,
-                               tick=self.gstate if validate else None)
+                               tick=self.gstate if validate else None,
+                               tiles=self.rscanner.pending)
         if self.gstate is not None and not validate:
             self.gstate[1:].add_(1)
         self.last = (self.idx, rep, rx, ft)

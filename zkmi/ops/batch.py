@@ -313,6 +313,35 @@ class FrameTable:
                 'overflow': bool(r[3])}
 
 
+# frame_scan flag: rows deferred (csrc/kernels/frame_scan.hip FS_DEFER)
+FS_DEFER = 1 << 24
+# streams of one tile at most take K1's single-launch path: no tile lists
+FS_TILE = 4096
+
+
+@dataclass
+class FrameTiles:
+    """The pending rows of a rows-deferred scan (``FrameScanner.scan(...,
+    rows=False)``): what the fused consumers (``decode_replies(...,
+    tiles=)``, the GPU server's fused serve) take instead of the frame
+    table's rows.  The consumer writes the rows into ``table`` and clears
+    the scan's flags; :meth:`consumed` tells the scanner so."""
+    scanner: object
+    buf: torch.Tensor
+    n_dev: object            # device int64 stream length, or None
+    ncap: int
+    ws: torch.Tensor
+    table: object            # the scanner's FrameTable
+
+    def consumed(self):
+        """A fused consumer ran on the scan's workspace: the next scan over
+        the same capacity needs no memset."""
+        sc = self.scanner
+        if sc.pending is self:
+            sc.pending = None
+            sc.clean_for = self.ncap
+
+
 FS_WINDOWS = (256, 512, 1024, 2048)
 # frame_window() values with this bit ask K1 for its long-frame mode: the
 # window is below the stream's largest frame, so fs_tile runs its frontier
@@ -390,13 +419,23 @@ class FrameScanner:
         self.ws = torch.empty(0, dtype=U8, device=device)
         self.ws_for = -1            # stream length the workspace covers
         self.clean_for = -1         # n_cap whose flags the last scan cleared
+        self.pending = None         # a deferred scan's rows not yet consumed
+        self.last_clean = False     # did the last scan skip its memset
 
-    def scan(self, buf, n, stream=None, nospec=False, misspec=0):
+    def scan(self, buf, n, stream=None, nospec=False, misspec=0, rows=True):
         """Frame ``buf[:n]``; ``n`` may be a device int64 length (see
         :func:`frame_scan`) — then nothing is read back to the host.
         ``nospec`` (tests): no tile takes a speculated entry, every link
         goes through the repair; ``misspec`` = P > 0 (tests): every P-th
-        tile takes a garbage entry (one byte past the speculated one)."""
+        tile takes a garbage entry (one byte past the speculated one).
+
+        ``rows=False``: the rows pass is deferred to the table's first
+        reader.  ``result`` is as always, but ``off`` / ``length`` are
+        written, and the workspace's flags cleared, by the fused consumer
+        that takes ``self.pending`` (a :class:`FrameTiles`).  Until one has,
+        the next scan cannot run clean.  A stream of one tile at most is
+        scanned in one launch either way: ``self.pending`` is then None and
+        the plain consumers apply."""
         L = _lib.lib()
         n_dev, ncap = _scan_len(buf, n)
         if ncap > self.ws_for:
@@ -407,16 +446,28 @@ class FrameScanner:
             self.ws_for = cover
             self.clean_for = -1
         t = self.table
+        if self.pending is not None:
+            # a deferred scan nobody consumed left its flags set
+            self.pending = None
+            self.clean_for = -1
+        defer = not rows and ncap > FS_TILE
         # a scan leaves its workspace's flags cleared for the next scan over
         # the same capacity (the layout depends on it): no memset then
+        self.last_clean = ncap == self.clean_for
         with _on(stream):
             L.frame_scan(buf, n_dev, ncap, self.max_packet, self.ws, t.off,
                          t.length, t.result, int(self.window),
-                         ncap == self.clean_for,
+                         self.last_clean,
                          (1 if nospec else 0) | (int(misspec) << 8) |
-                         ((self.group - 1) << 4))
-        self.clean_for = ncap
+                         ((self.group - 1) << 4) |
+                         (FS_DEFER if defer else 0))
         self.last_cap = ncap
+        if defer:
+            # clean again once a fused consumer has run (FrameTiles.consumed)
+            self.clean_for = -1
+            self.pending = FrameTiles(self, buf, n_dev, ncap, self.ws, t)
+        else:
+            self.clean_for = ncap
         return t
 
     def chain_stats(self, stream=None):
@@ -511,8 +562,13 @@ def alloc_replies(cap, device):
 
 
 def decode_replies(buf, frames, xid_table, out=None, stream=None,
-                   check=None, tick=None):
+                   check=None, tick=None, tiles=None):
     """K2-K8: decode every frame of ``frames`` as a reply.
+
+    ``tiles``: the :class:`FrameTiles` of a rows-deferred scan of ``buf``
+    whose table is ``frames`` (``scanner.pending``; None: the plain decode):
+    the decode reads the scan's tile lists, and writes the table's rows
+    itself.
 
     ``check = (idx, xid, data_len, acc[, slab, slot_off])``: also count, in
     the same kernel, the replies that are clean GET_DATA successes for the
@@ -527,6 +583,27 @@ def decode_replies(buf, frames, xid_table, out=None, stream=None,
     if out is None:
         out = alloc_replies(cap, buf.device)
     out.count = frames.count
+    if tiles is not None:
+        if tiles.table is not frames or \
+                tiles.buf.data_ptr() != buf.data_ptr():
+            raise ValueError('decode_replies: tiles of another scan')
+        with _on(stream):
+            if check is None:
+                L.decode_replies_tiles(buf, tiles.n_dev, tiles.ncap, tiles.ws,
+                                       frames.off, frames.length,
+                                       frames.count, xid_table.tab,
+                                       xid_table.mask, out.tensors())
+            else:
+                idx, xid, data_len, acc = check[:4]
+                slab, slot_off = check[4:6] if len(check) > 4 else (None,
+                                                                    None)
+                L.decode_replies_check_tiles(
+                    buf, tiles.n_dev, tiles.ncap, tiles.ws, frames.off,
+                    frames.length, frames.count, xid_table.tab,
+                    xid_table.mask, out.tensors(), idx, xid, data_len, acc,
+                    tick, slab, slot_off)
+        tiles.consumed()
+        return out
     with _on(stream):
         if check is None:
             L.decode_replies(buf, frames.off, frames.length, frames.count,
