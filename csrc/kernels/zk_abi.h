@@ -354,6 +354,27 @@ int zk_tree_acl_get(const ZkTree*, const ZkAclTable*, const uint8_t*,
                     const int64_t*, const int32_t*, const int64_t*, int64_t,
                     uint8_t*, int64_t, uint8_t*, int64_t, int64_t*, int64_t*,
                     int32_t*, int32_t, hipStream_t);
+// Mixed batches (tree_mix.hip).  The split: workspace bytes for ncap frames;
+// (rx, frames, count, ncap, has_acl, cls[ncap], sub[ncap], foff_c[3][ncap],
+// flen_c[3][ncap], counts[3], workspace + bytes).  The merge: workspace bytes;
+// (cls, sub, count, counts, ncap, then per class c of 3 the engine's stream,
+// its buffer's bytes, rec_off_c, total_c, err_c, workspace + bytes, out +
+// capacity, rec_off[ncap], total, err, terminate), with zk_tree_list's
+// conventions.  zk_tree_mix_small / _wave: the copy's tier bounds (bytes).
+int64_t zk_tree_mix_small(void);
+int64_t zk_tree_mix_wave(void);
+int64_t zk_tree_mix_split_workspace(int64_t ncap);
+int zk_tree_mix_split(const uint8_t*, const int64_t*, const int32_t*,
+                      const int64_t*, int64_t, int32_t, int32_t*, int32_t*,
+                      int64_t*, int32_t*, int64_t*, uint8_t*, int64_t,
+                      hipStream_t);
+int64_t zk_tree_mix_merge_workspace(int64_t ncap);
+int zk_tree_mix_merge(const int32_t*, const int32_t*, const int64_t*,
+                      const int64_t*, int64_t, const uint8_t* const*,
+                      const int64_t*, const int64_t* const*,
+                      const int64_t* const*, const int32_t* const*, uint8_t*,
+                      int64_t, uint8_t*, int64_t, int64_t*, int64_t*, int32_t*,
+                      int32_t, hipStream_t);
 int zk_bench_gen_get(int64_t, uint64_t, int64_t, int64_t, int32_t,
                      const int64_t*, int64_t*, int32_t*, int64_t*, int32_t*,
                      const int64_t*, int64_t*, int64_t*, hipStream_t);

@@ -1054,6 +1054,98 @@ void tree_acl_get(const std::vector<Tensor>& t,
          "tree_acl_get");
 }
 
+// Mixed batches (tree_mix.hip): the split of a batch's frame table by engine
+// class and the merge of the engines' reply streams into request order.
+int64_t tree_mix_split_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_mix_split_workspace n");
+  return zk_tree_mix_split_workspace(n);
+}
+
+int64_t tree_mix_merge_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_mix_merge_workspace n");
+  return zk_tree_mix_merge_workspace(n);
+}
+
+int64_t tree_mix_small() { return zk_tree_mix_small(); }
+int64_t tree_mix_wave() { return zk_tree_mix_wave(); }
+
+uint8_t* mix_ws(const Tensor& ws, int64_t bytes, const Tensor* d) {
+  uint8_t* w = P<uint8_t>(ws, U8, bytes, "mix workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w) % 16 == 0,
+              "zkmi: mix workspace must be 16-byte aligned");
+  return w;
+}
+
+// foff_c / flen_c: [3 * ncap], class c's table at c * ncap
+void tree_mix_split(const Tensor& rx, const Tensor& foff, const Tensor& flen,
+                    const Tensor& n_dev, int64_t ncap, bool has_acl,
+                    const Tensor& cls, const Tensor& sub,
+                    const Tensor& foff_c, const Tensor& flen_c,
+                    const Tensor& counts, const Tensor& ws) {
+  const Tensor* d = &rx;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: tree_mix ncap");
+  hip_ok(zk_tree_mix_split(
+             P<uint8_t>(rx, U8, 1, "rx"),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, has_acl ? 1 : 0,
+             P<int32_t>(cls, I32, ncap, "cls", d),
+             P<int32_t>(sub, I32, ncap, "sub", d),
+             P<int64_t>(foff_c, I64, 3 * ncap, "frame_off_c", d),
+             P<int32_t>(flen_c, I32, 3 * ncap, "frame_len_c", d),
+             P<int64_t>(counts, I64, 3, "counts", d),
+             mix_ws(ws, zk_tree_mix_split_workspace(ncap), d), ws.numel(),
+             cur_stream()),
+         "tree_mix_split");
+}
+
+// streams / rec_offs / totals / errs: one tensor per class (serve, GET_ACL,
+// list); a stream's capacity is its tensor's length
+void tree_mix_merge(const Tensor& cls, const Tensor& sub, const Tensor& n_dev,
+                    const Tensor& counts, int64_t ncap,
+                    const std::vector<Tensor>& streams,
+                    const std::vector<Tensor>& rec_offs,
+                    const std::vector<Tensor>& totals,
+                    const std::vector<Tensor>& errs, const Tensor& out,
+                    int64_t out_cap, const Tensor& rec_off,
+                    const Tensor& total, const Tensor& err, bool terminate,
+                    const Tensor& ws) {
+  const Tensor* d = &cls;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 28), "zkmi: tree_mix ncap");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_mix_merge out_cap");
+  need(streams, 3, "mix streams");
+  need(rec_offs, 3, "mix rec_offs");
+  need(totals, 3, "mix totals");
+  need(errs, 3, "mix errs");
+  const uint8_t* sp[3];
+  int64_t cap[3];
+  const int64_t* ro[3];
+  const int64_t* tp[3];
+  const int32_t* ep[3];
+  uint8_t* o = P<uint8_t>(out, U8, out_cap, "out", d);
+  for (int c = 0; c < 3; ++c) {
+    sp[c] = P<uint8_t>(streams[c], U8, 1, "mix stream", d);
+    cap[c] = streams[c].numel();
+    // (the copy reads a stream while it writes out)
+    TORCH_CHECK(sp[c] + cap[c] <= o || o + out.numel() <= sp[c],
+                "zkmi: tree_mix_merge out overlaps a stream");
+    ro[c] = P<int64_t>(rec_offs[c], I64, ncap, "mix rec_off", d);
+    tp[c] = P<int64_t>(totals[c], I64, 1, "mix total", d);
+    ep[c] = P<int32_t>(errs[c], I32, 1, "mix err", d);
+  }
+  hip_ok(zk_tree_mix_merge(
+             P<int32_t>(cls, I32, ncap, "cls"),
+             P<int32_t>(sub, I32, ncap, "sub", d),
+             P<int64_t>(n_dev, I64, 1, "count", d),
+             P<int64_t>(counts, I64, 3, "counts", d), ncap, sp, cap, ro, tp,
+             ep, mix_ws(ws, zk_tree_mix_merge_workspace(ncap), d), ws.numel(),
+             o, out_cap, P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_mix_merge");
+}
+
 void tree_expire(const std::vector<Tensor>& t, int64_t session, int64_t ncap,
                  const Tensor& removed) {
   ZkTree s = tree(t);
@@ -1447,6 +1539,19 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
         "bool terminate=False) -> ()",
         &tree_list);
+  m.def("tree_mix_split_workspace(int n) -> int", &tree_mix_split_workspace);
+  m.def("tree_mix_merge_workspace(int n) -> int", &tree_mix_merge_workspace);
+  m.def("tree_mix_small() -> int", &tree_mix_small);
+  m.def("tree_mix_wave() -> int", &tree_mix_wave);
+  m.def("tree_mix_split(Tensor rx, Tensor frame_off, Tensor frame_len, "
+        "Tensor count, int ncap, bool has_acl, Tensor(a!) cls, "
+        "Tensor(b!) sub, Tensor(c!) frame_off_c, Tensor(d!) frame_len_c, "
+        "Tensor(e!) counts, Tensor(f!) ws) -> ()", &tree_mix_split);
+  m.def("tree_mix_merge(Tensor cls, Tensor sub, Tensor count, Tensor counts, "
+        "int ncap, Tensor[] streams, Tensor[] rec_offs, Tensor[] totals, "
+        "Tensor[] errs, Tensor(a!) out, int out_cap, Tensor(b!) rec_off, "
+        "Tensor(c!) total, Tensor(d!) err, bool terminate, Tensor(e!) ws) "
+        "-> ()", &tree_mix_merge);
   m.def("tree_acl_workspace(int n) -> int", &tree_acl_workspace);
   m.def("tree_acl_record(Tensor(a!)[] acl, Tensor rx, Tensor frame_off, "
         "Tensor frame_len, Tensor count, int ncap, Tensor r_op, "

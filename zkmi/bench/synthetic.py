@@ -418,6 +418,14 @@ class GpuTree(object):
         return r.read_buffer(), st
 
 
+class _SubFrames(object):
+    """One engine's class of a mixed batch: the compacted frame table the
+    split wrote (``off``, ``length``) and its device ``count``."""
+
+    def __init__(self, off, length, count):
+        self.off, self.length, self.count = off, length, count
+
+
 class GpuServer(object):
     """Server half of the pipeline: frame-scan + decode requests, apply them
     to a :class:`GpuTree`, encode replies."""
@@ -573,28 +581,37 @@ class GpuServer(object):
         On a tree with an ACL table (``GpuTree(acl_cap=...)``) every
         successful CREATE's ACL is recorded after the serve (two launches,
         csrc/kernels/tree_acl.hip).  A GET_ACL in the batch is answered
-        UNIMPLEMENTED here: GET_ACL batches go through :meth:`serve_acl`."""
+        UNIMPLEMENTED here: GET_ACL batches go through :meth:`serve_acl`,
+        batches that mix it (or the list ops) with these through
+        :meth:`serve_mixed`."""
         for _ in self.serve_steps(rx, n, session, terminate, ordered, passes,
                                   wslot, resume):
             pass
         return self.result
 
     def serve_steps(self, rx, n, session=0, terminate=False, ordered=False,
-                    passes=4, wslot=-1, resume=False):
+                    passes=4, wslot=-1, resume=False, frames=None):
         """:meth:`serve` as a generator yielding once, between the request
         decode and the tree; the return tuple lands in ``self.result`` (a
         pipelined caller interleaves another connection's work there).
 
-"""
+        ``frames``: a frame table of ``rx`` to serve instead of scanning
+        ``rx[:n]`` (``off``, ``length`` and a device ``count``:
+        :meth:`serve_mixed` passes the serve's class of the batch); the
+        reply frame starts then go to ``self.mix_rec_off[0]``."""
         L = _lib.lib()
         if self.fused_rows and (ordered or resume or self.seq_order or
-                                self.tree.acl is not None):
+                                self.tree.acl is not None or
+                                frames is not None):
             raise ValueError('fused_rows: the serve must be the first '
                              'reader of the frame table (not ordered, no '
                              'seq_order, no ACL table, no watch resume)')
-        ft = self.scanner.scan(rx, n, rows=not self.fused_rows)
-        # (None for a request stream of one tile at most: the plain serve)
-        tiles = self.scanner.pending
+        if frames is not None:
+            ft, tiles = frames, None
+        else:
+            ft = self.scanner.scan(rx, n, rows=not self.fused_rows)
+            # (None for a request stream of one tile at most: the plain serve)
+            tiles = self.scanner.pending
         # ordered serving ranks the batch from K12's request table; the
         # plain serve parses each frame in registers instead
         rt = B.decode_requests(rx, ft, out=self.rt) if ordered else None
@@ -640,7 +657,8 @@ class GpuServer(object):
         out, rec_off, total, err = B.encode_responses(
             r, self.tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
-            total_err=self.total_err, prescanned=not ordered)
+            total_err=self.total_err, prescanned=not ordered,
+            rec_off=self.mix_rec_off[0] if frames is not None else None)
         if self.tree.compact_free:
             self.tree.free_compact()
         self.last_rec_off = rec_off         # reply frame starts (R2 splits)
@@ -670,7 +688,7 @@ class GpuServer(object):
         bytes (default: K1's 16 MiB cap) is answered SYSTEMERROR.  ``err``
         2 with ``total`` 0: the replies did not fit ``out`` (default: the
         server's reply buffer) and nothing was written.  Mixed batches go
-        through :meth:`serve`, which answers these two ops UNIMPLEMENTED.
+        through :meth:`serve_mixed`.
 
         A sharded tree (``shard`` with world > 1) raises: its parents count
         children it does not index."""
@@ -678,16 +696,7 @@ class GpuServer(object):
         if tree.shard is not None and tree.shard[1] > 1:
             raise ValueError('serve_list: a sharded tree does not index '
                              'every child of its parents')
-        dev = tree.device
-        if getattr(self, 'list_want', None) is None:
-            self.list_want = torch.full((tree.cap,), _lib.LIST_IDLE,
-                                        dtype=I32, device=dev)
-            self.list_ws = torch.empty(
-                _lib.tree_list_workspace(self.cap_frames), dtype=U8,
-                device=dev)
-            self.list_rec_off = torch.empty(self.cap_frames, dtype=I64,
-                                            device=dev)
-            self.list_total_err = B._total_err(dev)
+        self._list_buffers()
         if out is None:
             out = self.out
         if max_frame is None:
@@ -701,6 +710,28 @@ class GpuServer(object):
         self.last_rec_off = self.list_rec_off
         self.result = (out, total, err, ft)
         return self.result
+
+    def _list_buffers(self):
+        """The list engine's buffers, allocated on first use."""
+        if getattr(self, 'list_want', None) is not None:
+            return
+        dev = self.tree.device
+        self.list_want = torch.full((self.tree.cap,), _lib.LIST_IDLE,
+                                    dtype=I32, device=dev)
+        self.list_ws = torch.empty(
+            _lib.tree_list_workspace(self.cap_frames), dtype=U8, device=dev)
+        self.list_rec_off = torch.empty(self.cap_frames, dtype=I64,
+                                        device=dev)
+        self.list_total_err = B._total_err(dev)
+
+    def _acl_buffers(self):
+        """The GET_ACL engine's buffers, allocated on first use."""
+        if getattr(self, 'acl_rec_off', None) is not None:
+            return
+        dev = self.tree.device
+        self.acl_rec_off = torch.empty(self.cap_frames, dtype=I64,
+                                       device=dev)
+        self.acl_total_err = B._total_err(dev)
 
     def _acl_workspace(self):
         if getattr(self, 'acl_ws', None) is None:
@@ -723,18 +754,14 @@ class GpuServer(object):
         table SYSTEMERROR (see :meth:`acl_stats`); all header only.  ``err``
         2 with ``total`` 0: the replies did not fit ``out`` (default: the
         server's reply buffer) and nothing was written.  Mixed batches go
-        through :meth:`serve`, which answers GET_ACL UNIMPLEMENTED.
+        through :meth:`serve_mixed`.
 
         Raises ``ValueError`` on a tree without an ACL table."""
         tree = self.tree
         if tree.acl is None:
             raise ValueError('serve_acl: the tree keeps no ACL table '
                              '(GpuTree(acl_cap=...))')
-        dev = tree.device
-        if getattr(self, 'acl_rec_off', None) is None:
-            self.acl_rec_off = torch.empty(self.cap_frames, dtype=I64,
-                                           device=dev)
-            self.acl_total_err = B._total_err(dev)
+        self._acl_buffers()
         if out is None:
             out = self.out
         ft = self.scanner.scan(rx, n)
@@ -744,6 +771,138 @@ class GpuServer(object):
                           out, out.numel(), self.acl_rec_off, total, err,
                           terminate)
         self.last_rec_off = self.acl_rec_off
+        self.result = (out, total, err, ft)
+        return self.result
+
+    def _mix_buffers(self):
+        """The split's and the merge's buffers and the two engines' scratch
+        streams, allocated on first use."""
+        if getattr(self, 'mix_cls', None) is not None:
+            return
+        dev = self.tree.device
+        cap = self.cap_frames
+        self.mix_cls = torch.empty(cap, dtype=I32, device=dev)
+        self.mix_sub = torch.empty(cap, dtype=I32, device=dev)
+        self.mix_foff = torch.empty(3 * cap, dtype=I64, device=dev)
+        self.mix_flen = torch.empty(3 * cap, dtype=I32, device=dev)
+        self.mix_counts = torch.zeros(3, dtype=I64, device=dev)
+        self.mix_frames = [
+            _SubFrames(self.mix_foff[c * cap:(c + 1) * cap],
+                       self.mix_flen[c * cap:(c + 1) * cap],
+                       self.mix_counts[c:c + 1]) for c in range(3)]
+        self.mix_split_ws = torch.empty(
+            max(_lib.tree_mix_split_workspace(cap), 16), dtype=U8, device=dev)
+        self.mix_merge_ws = torch.empty(
+            max(_lib.tree_mix_merge_workspace(cap), 16), dtype=U8, device=dev)
+        self._list_buffers()
+        self._acl_buffers()
+        # the serve's frame starts, then the merged ones
+        self.mix_rec_off = (torch.empty(cap, dtype=I64, device=dev),
+                            torch.empty(cap, dtype=I64, device=dev))
+        self.mix_total_err = B._total_err(dev)
+        # (a tree without an ACL table: the GET_ACL class stays empty)
+        self.acl_total_err[0].zero_()
+        self.acl_total_err[1].zero_()
+        self.mix_scratch = (
+            torch.empty(self.out.numel(), dtype=U8, device=dev)
+            if self.tree.acl is not None else None,
+            torch.empty(self.out.numel(), dtype=U8, device=dev))
+        self.mix_out = torch.empty(self.out.numel(), dtype=U8, device=dev)
+
+    def serve_mixed(self, rx, n, session=0, terminate=False, wslot=-1,
+                    resume=False, max_frame=None, out=None):
+        """Serve the request stream ``rx[:n]`` (``n`` a host length or a
+        device total) whatever ops it mixes — what a session pipelines on one
+        connection, what ``Client.bulk`` encodes — into one reply stream in
+        request order.  Returns ``(out, total, err, frame_table)`` like
+        :meth:`serve`, with the whole batch's frame table; ``out`` defaults
+        to a buffer of the server's reply capacity (``self.mix_out``, not
+        ``self.out``: the serve's own stream lands there).
+
+        One K1 scan, then the split of the frame table by engine
+        (csrc/kernels/tree_mix.hip): GET_CHILDREN / GET_CHILDREN2 to the
+        list engine, GET_ACL to the ACL engine (on a tree with an ACL table),
+        everything else — unknown opcodes, frames without an opcode word and
+        GET_ACL on a tree without an ACL table included — to the fused serve,
+        each answering as :meth:`serve_list`, :meth:`serve_acl` and
+        :meth:`serve` (unordered) do.  The merge puts the three reply
+        streams back into request order; ``self.last_rec_off`` holds the
+        merged frame starts.
+
+        The batch contract: the engines run in the fixed order serve,
+        GET_ACL, list, each over its requests in request order.  So the
+        writes of a batch are concurrent as in :meth:`serve` (``session``,
+        ``wslot`` and ``resume`` as there; ``self.notif`` is what the
+        batch's writes fired), and a GET_ACL or a list of a batch sees the
+        tree after all of that batch's writes: a list of a parent shows the
+        child created in the same batch and misses the one deleted in it, a
+        GET_ACL returns the ACL of a node created in the same batch.  A
+        ``watch=1`` list arms the child watch of slot ``wslot`` after the
+        batch's writes: they do not fire it, the next batch's do.  In-batch
+        ordering (``serve(ordered=True)``) is not offered.
+
+        ``max_frame``: as in :meth:`serve_list`.  ``err`` is the first
+        non-zero one of the serve's, the ACL engine's and the list engine's
+        encoders (each stream has the server's reply capacity), else 2 when
+        the merged stream does not fit ``out``; then ``total`` is 0 and
+        ``out`` is untouched.
+
+        A class without a member still costs its engine's launches: nothing
+        is read back that could skip them.  After the first call has
+        allocated the buffers a call without ``resume`` reads nothing back
+        and allocates nothing; it can be captured in a HIP graph on one
+        stream.
+
+        Raises ``ValueError`` on a ``fused_rows`` server (the split must be
+        the frame table's first reader) and on a sharded tree (``shard``
+        with world > 1), as :meth:`serve_list` does."""
+        tree = self.tree
+        if self.fused_rows:
+            raise ValueError('serve_mixed: a fused_rows server defers the '
+                             'frame table\'s rows to the serve; the split '
+                             'must be their first reader')
+        if tree.shard is not None and tree.shard[1] > 1:
+            raise ValueError('serve_mixed: a sharded tree does not index '
+                             'every child of its parents')
+        self._mix_buffers()
+        cap = self.cap_frames
+        if out is None:
+            out = self.mix_out
+        if max_frame is None:
+            max_frame = consts.MAX_PACKET
+        ft = self.scanner.scan(rx, n)
+        _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
+                            tree.acl is not None, self.mix_cls, self.mix_sub,
+                            self.mix_foff, self.mix_flen, self.mix_counts,
+                            self.mix_split_ws)
+        fa, fc, fl = self.mix_frames
+        for _ in self.serve_steps(rx, n, session, False, False, 4, wslot,
+                                  resume, frames=fa):
+            pass
+        a_out, a_total, a_err, _ = self.result
+        c_out, l_out = self.mix_scratch
+        c_total, c_err = self.acl_total_err
+        if tree.acl is not None:
+            _lib.tree_acl_get(tree.tensors, tree.acl, rx, fc.off, fc.length,
+                              fc.count, cap, self._acl_workspace(), c_out,
+                              c_out.numel(), self.acl_rec_off, c_total,
+                              c_err, False)
+        else:
+            c_out = l_out
+        l_total, l_err = self.list_total_err
+        _lib.tree_list(tree.tensors, rx, fl.off, fl.length, fl.count, cap,
+                       wslot, max_frame, self.list_want, self.list_ws, l_out,
+                       l_out.numel(), self.list_rec_off, l_total, l_err,
+                       False)
+        total, err = self.mix_total_err
+        _lib.tree_mix_merge(
+            self.mix_cls, self.mix_sub, ft.count, self.mix_counts, cap,
+            [a_out, c_out, l_out],
+            [self.mix_rec_off[0], self.acl_rec_off, self.list_rec_off],
+            [a_total, c_total, l_total], [a_err, c_err, l_err], out,
+            out.numel(), self.mix_rec_off[1], total, err, self.mix_merge_ws,
+            terminate)
+        self.last_rec_off = self.mix_rec_off[1]
         self.result = (out, total, err, ft)
         return self.result
 

@@ -165,5 +165,56 @@ def tree_acl_get(tree, acl, rx, frame_off, frame_len, count, ncap, ws, out,
                        bool(terminate))
 
 
+# engine classes of a mixed batch, in engine order (csrc/kernels/zk_mix.h):
+# the fused serve, the GET_ACL path, the list path
+MIX_A, MIX_C, MIX_L = 0, 1, 2
+
+
+def tree_mix_bounds():
+    """(small, wave): the tier bounds of the merge's copy kernels in bytes
+    (csrc/kernels/tree_mix.hip MIX_SMALL / MIX_WAVE)."""
+    return lib().tree_mix_small(), lib().tree_mix_wave()
+
+
+def tree_mix_split_workspace(ncap):
+    """Bytes of the workspace :func:`tree_mix_split` needs for ``ncap``
+    frames (a uint8 tensor; nothing in it needs zeroing)."""
+    return lib().tree_mix_split_workspace(int(ncap))
+
+
+def tree_mix_merge_workspace(ncap):
+    """Bytes of the workspace :func:`tree_mix_merge` needs for ``ncap``
+    requests (a uint8 tensor; nothing in it needs zeroing)."""
+    return lib().tree_mix_merge_workspace(int(ncap))
+
+
+def tree_mix_split(rx, frame_off, frame_len, count, ncap, has_acl, cls, sub,
+                   frame_off_c, frame_len_c, counts, ws):
+    """Split a batch's frame table by engine class, on the current stream
+    (csrc/kernels/tree_mix.hip): ``cls`` / ``sub`` (int32 [ncap]: class and
+    index inside the class; -1 / 0 past ``count``), the compacted tables
+    ``frame_off_c`` (int64) / ``frame_len_c`` (int32), both [3 * ncap] with
+    class c's at ``c * ncap``, and ``counts`` (int64 [3]).  Stable: request
+    order is kept inside a class.  No host read."""
+    lib().tree_mix_split(rx, frame_off, frame_len, count, int(ncap),
+                         bool(has_acl), cls, sub, frame_off_c, frame_len_c,
+                         counts, ws)
+
+
+def tree_mix_merge(cls, sub, count, counts, ncap, streams, rec_offs, totals,
+                   errs, out, out_cap, rec_off, total, err, ws,
+                   terminate=False):
+    """Merge the three engines' reply streams into request order, on the
+    current stream: request i takes reply ``sub[i]`` of stream ``cls[i]``
+    (``streams`` / ``rec_offs`` / ``totals`` / ``errs``: a tensor per class)
+    -> ``out[:total]``, the starts -> ``rec_off``.  An engine's non-zero
+    ``err`` is the merged one (class 0 first), else ``err`` 2 when the stream
+    does not fit ``out_cap``; then ``total`` is 0 and nothing is written."""
+    lib().tree_mix_merge(cls, sub, count, counts, int(ncap), list(streams),
+                         list(rec_offs), list(totals), list(errs), out,
+                         int(out_cap), rec_off, total, err, bool(terminate),
+                         ws)
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)

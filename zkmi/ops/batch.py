@@ -754,7 +754,7 @@ def response_workspace(cap, device):
 
 def encode_responses(resp, store, out_cap, out=None, stream=None,
                      presized=None, terminate=False, total_err=None,
-                     prescanned=False):
+                     prescanned=False, rec_off=None):
     """K13: server-mode reply encode -> (bytes, rec_off, total, err).
     ``store``: the node store's tensors [slab, slot_off, data_len,
     slot_cap] (:attr:`zkmi.bench.synthetic.GpuTree.store`).
@@ -762,7 +762,8 @@ def encode_responses(resp, store, out_cap, out=None, stream=None,
     already filled by the producer; the sizes pass is then skipped.
     ``total_err``: the (total, err) pair to write (default: new ones);
     ``prescanned``: the presized workspace's block bases and ``total`` were
-    already computed (the tree's finish_scan launch)."""
+    already computed (the tree's finish_scan launch).  ``rec_off``: the
+    int64 [cap] tensor the frame starts go to (default: a new one)."""
     L = _lib.lib()
     cap = resp.opcode.numel()
     dev = resp.opcode.device
@@ -771,7 +772,8 @@ def encode_responses(resp, store, out_cap, out=None, stream=None,
     else:
         sizes = torch.empty(cap, dtype=I64, device=dev)
         ws = torch.empty(L.scan_workspace(cap), dtype=I64, device=dev)
-    rec_off = torch.empty(cap, dtype=I64, device=dev)
+    if rec_off is None:
+        rec_off = torch.empty(cap, dtype=I64, device=dev)
     total, err = total_err if total_err is not None else _total_err(dev)
     if out is None:
         out = torch.empty(out_cap, dtype=U8, device=dev)
