@@ -252,7 +252,10 @@ ZK_DEV int32_t do_create(const ZkTree& t, Lane& L, const uint8_t* data,
   if (ins != v) {
     // the child was not made (the cversion it took stays: a gap)
     if (taken) cn_add(t, par, 0, -1);
-    return ins == TREE_INSERT_TIMEOUT ? ERR_SYSTEM : ERR_NODE_EXISTS;
+    // (-1: the probe met no empty entry and no tombstone of this key — an
+    // index full of other names' tombstones, cured by a rebuild; the name
+    // itself does not exist)
+    return ins < 0 ? ERR_SYSTEM : ERR_NODE_EXISTS;  // (or the timeout)
   }
   t.eph[v] = eph ? session : 0;
   if (par >= 0) {
@@ -480,14 +483,17 @@ ZK_DEV void tree_serve_body(
         const Found f = tree_lookup(t, L.path, L.pl);
         const int64_t node = f.node, so = f.slot;
         if (node < 0) { L.err = ERR_NO_NODE; break; }
-        if (cn_nchild(__hip_atomic_load(&t.cn[node], __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT)) > 0) {
-          L.err = ERR_NOT_EMPTY;
-          break;
-        }
+        // the version before the children, as ZooKeeper checks them (a
+        // stale delete of a parent with children is BAD_VERSION)
+        const int32_t nkids = cn_nchild(__hip_atomic_load(
+            &t.cn[node], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         const int32_t want = L.flags;
         if (want != -1 && ld_be32(s.slab + so + 32) != want) {
           L.err = ERR_BAD_VERSION;
+          break;
+        }
+        if (nkids > 0) {
+          L.err = ERR_NOT_EMPTY;
           break;
         }
         if (!tree_erase_at(t, f.ent, node)) { L.err = ERR_NO_NODE; break; }

@@ -374,6 +374,18 @@ ZK_DEV int64_t tree_insert(const ZkTree& t, int64_t v, const uint8_t* p,
     // another line each (keys only ever go 0 -> key within a launch, so a
     // stale 0 just means the CAS below answers); REUSE has just loaded it
     int64_t k = REUSE ? k0 : *ht_key(t, s);
+    if (!REUSE && k == 0 && tomb >= 0) {
+      // the chain ends without the path: take the tombstone of its key
+      // passed on the way (below)
+      if (atomicCAS((unsigned long long*)ht_val(t, tomb),
+                    (unsigned long long)tv, 0ull) == (unsigned long long)tv) {
+        ent_fill(t, tomb, p, n, dl);
+        __hip_atomic_store(ht_val(t, tomb), pv, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        return v;
+      }
+      tomb = -1;                       // taken meanwhile: the empty slot
+    }
     if (k == 0)
       k = atomicCAS((unsigned long long*)ht_key(t, s), 0ull,
                     (unsigned long long)key);
@@ -390,23 +402,54 @@ ZK_DEV int64_t tree_insert(const ZkTree& t, int64_t v, const uint8_t* p,
         w = __hip_atomic_load(ht_val(t, s), __ATOMIC_RELAXED,
                               __HIP_MEMORY_SCOPE_AGENT);
       if (w == 0) return TREE_INSERT_TIMEOUT;
-      if (w > 0) {
+      // the entry's path against this one: of a live entry, and of a
+      // tombstone whose words hold a whole path (below)
+      const bool live = w > 0;
+      bool same = false;
+      if (live || (!REUSE && n <= EN_PATH)) {
         int64_t e[HT_W];
         ent_load(t, s, e);
-        if (ent_is(t, e, val_node(w), p, n)) return val_node(w);
+        same = ent_is(t, e, live ? val_node(w) : 0, p, n);
       }
-      // a tombstone of the same key: claim it (0 while its words are
-      // rewritten), then publish
-      if (val_tomb(w) &&
-          atomicCAS((unsigned long long*)ht_val(t, s), (unsigned long long)w,
-                    0ull) == (unsigned long long)w) {
-        ent_fill(t, s, p, n, dl);
-        __hip_atomic_store(ht_val(t, s), pv, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        return v;
+      if (live && same) return val_node(w);
+      // a tombstone of the same key.  The path may still live further down
+      // the chain — another path of the same key went first, and this
+      // tombstone is that one's (two paths of one 64-bit key are rare, but
+      // a client can make them up) — so the first such tombstone is only
+      // remembered and taken where the chain ends.  Claimed at once (0
+      // while its words are rewritten, then published): REUSE, where the
+      // caller vouches that the name is new, and a tombstone that still
+      // holds this very path — a DELETE writes only the val, and a path of
+      // up to EN_PATH bytes is whole in the entry — which is the path's
+      // own: a path is indexed once and a moved entry's copy lies before
+      // the tombstone it leaves, so the path lives nowhere after it (the
+      // usual re-create of a deleted name: no probe to the chain's end)
+      if (val_tomb(w)) {
+        if (!REUSE && !same) {
+          if (tomb < 0) {
+            tomb = s;
+            tv = w;
+          }
+        } else if (atomicCAS((unsigned long long*)ht_val(t, s),
+                             (unsigned long long)w, 0ull) ==
+                   (unsigned long long)w) {
+          ent_fill(t, s, p, n, dl);
+          __hip_atomic_store(ht_val(t, s), pv, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+          return v;
+        }
       }
     }
     s = (s + 1) & t.mask;
+  }
+  // no empty entry: the tombstone of this key, if the probe passed one
+  if (!REUSE && tomb >= 0 &&
+      atomicCAS((unsigned long long*)ht_val(t, tomb), (unsigned long long)tv,
+                0ull) == (unsigned long long)tv) {
+    ent_fill(t, tomb, p, n, dl);
+    __hip_atomic_store(ht_val(t, tomb), pv, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    return v;
   }
   return -1;
 }
