@@ -832,10 +832,25 @@ __global__ __launch_bounds__(NT) void tree_finish_scan_k(
 // DBG: phase clocks into dbg (zk_tree_expire_debug), 100 MHz ticks — an
 // instance of its own: the clock reads in the plain kernel, even behind a
 // null test, took the expiry from ~0.45 to ~1 ms.
-template <bool DBG>
-__global__ __launch_bounds__(TR_T) void tree_expire_k(
-    ZkTree t, int64_t session, int64_t ncap,
-    unsigned long long* __restrict__ removed, int32_t* __restrict__ dbg) {
+//
+// WT: the instance for a tree with a watch table (chosen on the host by
+// wt_key != nullptr).  Every removed node fires what a DELETE fires — its
+// data mask, its child mask (a watcher in both is told once) and its
+// parent's child mask — and a removal that fired anything appends one
+// compact record (WT_REC words, the serve's `fired` layout) at rec + 8;
+// rec[0] counts the records wanted, rec_cap is the room (records past it
+// are dropped: the caller compares the two).  zk_watch_events expands them as
+// it does a batch's.  The plain instance is a kernel of its own and comes
+// out as before (same registers, LDS and code size).  The same fire behind
+// a run-time null test of wt_key took the plain kernel from 40 to 46 VGPRs,
+// 76 to 88 SGPRs and 4708 to 6880 bytes of code (occupancy 8 either way;
+// the resource table, not timed — the phase clocks above are why a test
+// that costs nothing on paper is not trusted in this kernel).
+template <bool DBG, bool WT>
+ZK_DEV void tree_expire_body(
+    const ZkTree& t, int64_t session, int64_t ncap,
+    unsigned long long* __restrict__ removed, int32_t* __restrict__ dbg,
+    int64_t* __restrict__ rec, int64_t rec_cap) {
   session = sess_of(t, session);
   const int64_t v = (int64_t)blockIdx.x * TR_T + threadIdx.x;
   const int64_t c0 = DBG ? (int64_t)wall_clock64() : 0;
@@ -872,6 +887,27 @@ __global__ __launch_bounds__(TR_T) void tree_expire_k(
       par = p0;
       if (par >= 0) parent_touch(t, par, -1, true, zx);
       t.eph[v] = 0;
+      if (WT) {
+        const int64_t ws = wt_find(t, t.path_arena + poff, plen);
+        const uint64_t m0 = wt_fire_at(t, ws, WK_DATA);
+        const uint64_t m1 = wt_fire_at(t, ws, WK_CHILD) & ~m0;
+        const int64_t ppw = par >= 0 ? t.node_pw[par] : 0;
+        const uint64_t m2 =
+            par >= 0 ? wt_fire(t, node_path(t, ppw), pw_len(ppw), WK_CHILD)
+                     : 0;
+        if ((m0 | m1 | m2) != 0 && rec != nullptr) {
+          const int64_t k = (int64_t)atomicAdd((unsigned long long*)&rec[0],
+                                               1ull);
+          if (k < rec_cap) {
+            int64_t* f = rec + 8 + (int64_t)WT_REC * k;
+            f[0] = (int64_t)m0;
+            f[1] = (int64_t)m1;
+            f[2] = (int64_t)m2;
+            f[3] = pw_pack(poff, plen);
+            f[4] = ppw;
+          }
+        }
+      }
     }
   }
   // the frees' ticket also counts `removed` (no second block round)
@@ -885,6 +921,21 @@ __global__ __launch_bounds__(TR_T) void tree_expire_k(
     dbg[4 * v + 2] = (int32_t)(c2 - c1);
     dbg[4 * v + 3] = (int32_t)(c3 - c0);
   }
+}
+
+template <bool DBG>
+__global__ __launch_bounds__(TR_T) void tree_expire_k(
+    ZkTree t, int64_t session, int64_t ncap,
+    unsigned long long* __restrict__ removed, int32_t* __restrict__ dbg) {
+  tree_expire_body<DBG, false>(t, session, ncap, removed, dbg, nullptr, 0);
+}
+
+__global__ __launch_bounds__(TR_T) void tree_expire_wt_k(
+    ZkTree t, int64_t session, int64_t ncap,
+    unsigned long long* __restrict__ removed, int64_t* __restrict__ rec,
+    int64_t rec_cap) {
+  tree_expire_body<false, true>(t, session, ncap, removed, nullptr, rec,
+                                rec_cap);
 }
 
 int finish_launch(const ZkTree* t, const int64_t* n_dev, int64_t bump,
@@ -918,11 +969,18 @@ int zk_tree_finish_scan(const ZkTree* t, const int64_t* n_dev, int64_t bump,
 static int32_t* g_exp_dbg = nullptr;
 void zk_tree_expire_debug(int32_t* buf) { g_exp_dbg = buf; }
 
+// rec (a tree with a watch table; may be null: the fired masks are then
+// consumed without a record): [0] records wanted (zeroed by the caller),
+// [8 + WT_REC * k) record k < rec_cap.
 int zk_tree_expire(const ZkTree* t, int64_t session, int64_t ncap,
-                   unsigned long long* removed, hipStream_t st) {
+                   unsigned long long* removed, int64_t* rec, int64_t rec_cap,
+                   hipStream_t st) {
   if (ncap <= 0) return 0;
   const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
-  if (g_exp_dbg != nullptr)
+  if (t->wt_key != nullptr)
+    zk::tree_expire_wt_k<<<nb, zk::TR_T, 0, st>>>(*t, session, ncap, removed,
+                                                  rec, rec_cap);
+  else if (g_exp_dbg != nullptr)
     zk::tree_expire_k<true><<<nb, zk::TR_T, 0, st>>>(*t, session, ncap, removed,
                                                      g_exp_dbg);
   else

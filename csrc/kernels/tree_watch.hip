@@ -1,6 +1,8 @@
-// The GPU tree's watch events: the masks a served batch fired expanded into
-// notifications, and the SET_WATCHES catch-up (the watch table itself, wt_arm
-// / wt_fire: zk_tree.h).
+// The GPU tree's watch events: the masks a served batch (or a session expiry)
+// fired expanded into notifications, the SET_WATCHES catch-up, and the watch
+// table's maintenance: a closed session's bits dropped, the table rebuilt
+// from the entries that still hold a watch (the table itself, wt_arm /
+// wt_fire: zk_tree.h).
 #include "zk_tree.h"
 
 namespace zk {
@@ -104,8 +106,9 @@ __global__ __launch_bounds__(WR_T) void wt_resume_k(
     int32_t* __restrict__ ev_type, int64_t* __restrict__ ev_poff,
     int32_t* __restrict__ ev_plen, int64_t* __restrict__ out) {
   __shared__ int64_t sm[WR_T / 64 + 1];
-  __shared__ int64_t s_n, s_rel;
+  __shared__ int64_t s_n, s_rel, s_drop;
   int64_t o = 0, rearmed = 0;
+  if (threadIdx.x == 0) s_drop = 0;
   const int64_t nfr = min(*n_dev, ncap);
   for (int64_t fr = 0; fr < nfr; ++fr) {
     // thread 0 lists the frame's paths (kind << 62 | off << 24 | len);
@@ -113,13 +116,21 @@ __global__ __launch_bounds__(WR_T) void wt_resume_k(
     if (threadIdx.x == 0) {
       const ReqFields rq = parse_request(rx, foff[fr], flen[fr]);
       int64_t m = 0;
+      // (a count or a length that runs past the frame ends the listing: a
+      // listed path takes at least its 4 length bytes of the frame, so
+      // ent_cap = stream bytes / 4 holds every frame's list)
       if (rq.status == ST_OK && rq.op == OP_SET_WATCHES) {
+        const int64_t end = foff[fr] + flen[fr];
         int64_t k = rq.voff;
-        for (int g = 0; g < 3; ++g) {
+        for (int g = 0; g < 3 && k + 4 <= end; ++g) {
           const int32_t c = max(ld_be32(rx + k), 0);
           k += 4;
-          for (int32_t j = 0; j < c; ++j) {
+          for (int32_t j = 0; j < c && k + 4 <= end; ++j) {
             const int32_t l = max(ld_be32(rx + k), 0);
+            if (k + 4 + l > end) {
+              k = end;
+              break;
+            }
             if (m < ent_cap)
               ent[m] = ((int64_t)g << 62) | ((k + 4) << 24) | l;
             ++m;
@@ -128,6 +139,7 @@ __global__ __launch_bounds__(WR_T) void wt_resume_k(
         }
       }
       s_n = min(m, ent_cap);
+      s_drop += m - s_n;
       s_rel = rq.rel;
     }
     __syncthreads();
@@ -176,6 +188,45 @@ __global__ __launch_bounds__(WR_T) void wt_resume_k(
     out[0] = min(o, cap);        // events written
     out[1] = tot;                // watches re-armed
     out[2] = o;                  // events (> out[0]: overflow)
+    out[3] = s_drop;             // listed paths that found no room in ent
+  }
+}
+
+// ---- maintenance ------------------------------------------------------------
+// A closed session's watches go with it: clear watcher slot wslot's bit from
+// every mask (the entries stay; zk_watch_rebuild drops the empty ones).
+__global__ __launch_bounds__(TR_T) void wt_drop_k(ZkTree t, int32_t wslot) {
+  const unsigned long long keep = ~(1ull << wslot);
+  const int64_t n = 2 * (t.wt_hmask + 1);
+  for (int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * TR_T)
+    if (t.wt_mask[i] & ~keep) t.wt_mask[i] &= keep;
+}
+
+// Entries are never removed by a fire, so every path ever watched keeps one:
+// the rebuild inserts the old table's entries that still hold a watch into
+// the tree's new (zeroed) table by their two hash words; the counters move
+// with them.  Entries that find no room (a smaller table) are counted lost.
+__global__ __launch_bounds__(TR_T) void wt_rebuild_k(
+    ZkTree t, const int64_t* __restrict__ okey,
+    const int64_t* __restrict__ omask, int64_t ohmask) {
+  const int64_t on = ohmask + 1;
+  unsigned long long* stat = &t.wt_mask[2 * (t.wt_hmask + 1)];
+  for (int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x; i < on;
+       i += (int64_t)gridDim.x * TR_T) {
+    if (i < WT_STATS && omask[2 * on + i] != 0)
+      atomicAdd(&stat[i], (unsigned long long)omask[2 * on + i]);
+    const int64_t k = okey[2 * i], g = okey[2 * i + 1];
+    const int64_t m0 = omask[2 * i], m1 = omask[2 * i + 1];
+    if (k == 0 || g == 0 || (m0 | m1) == 0) continue;
+    const int64_t s = wt_slot(t, (uint64_t)k, (uint64_t)g, true);
+    if (s < 0) {
+      atomicAdd(&stat[WS_LOST], (unsigned long long)(__popcll(m0) +
+                                                    __popcll(m1)));
+      continue;
+    }
+    t.wt_mask[2 * s] = (unsigned long long)m0;
+    t.wt_mask[2 * s + 1] = (unsigned long long)m1;
   }
 }
 
@@ -211,7 +262,9 @@ int zk_watch_events(const int32_t* r_op, const int32_t* r_err,
 // resumed session with watcher slot wslot: events (ev_type, ev_poff /
 // ev_plen into rx) for what changed after each frame's relZxid, the other
 // watches re-armed.  out[0] = events written (<= cap), out[1] = re-armed
-// watches, out[2] = events.  ent: scratch for ent_cap paths.
+// watches, out[2] = events, out[3] = listed paths past ent_cap (neither
+// answered nor re-armed).  ent: scratch for ent_cap paths; the stream's
+// bytes / 4 hold any frame's list.
 int zk_watch_resume(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
                     const int32_t* flen, const int64_t* n_dev, int64_t ncap,
                     int32_t wslot, int64_t* ent, int64_t ent_cap, int64_t cap,
@@ -221,6 +274,26 @@ int zk_watch_resume(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
   zk::wt_resume_k<<<1, zk::WR_T, 0, st>>>(*t, rx, foff, flen, n_dev, ncap,
                                            wslot, ent, ent_cap, cap, ev_type,
                                            ev_poff, ev_plen, out);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_watch_drop(const ZkTree* t, int32_t wslot, hipStream_t st) {
+  if (t->wt_key == nullptr || wslot < 0 || wslot > 63) return -1;
+  const int64_t n = 2 * (t->wt_hmask + 1);
+  const int64_t nb = (n + zk::TR_T - 1) / zk::TR_T;
+  zk::wt_drop_k<<<(unsigned)(nb < 1024 ? nb : 1024), zk::TR_T, 0, st>>>(
+      *t, wslot);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_watch_rebuild(const ZkTree* t, const int64_t* okey,
+                     const int64_t* omask, int64_t ohmask, hipStream_t st) {
+  if (t->wt_key == nullptr || okey == t->wt_key) return -1;
+  const int64_t nb = (ohmask + zk::TR_T) / zk::TR_T;
+  zk::wt_rebuild_k<<<(unsigned)(nb < 1024 ? nb : 1024), zk::TR_T, 0, st>>>(
+      *t, okey, omask, ohmask);
   ZK_LAUNCH_CHECK();
   return 0;
 }

@@ -133,8 +133,12 @@ struct ZkTree {
   int32_t* node_path_cap;      // [cap] bytes of the node's path storage
   int64_t* eph;                // [cap] host-endian ephemeralOwner shadow
   // watch table (null wt_key: the tree keeps no watches), see wt_* below
-  int64_t* wt_key;             // [wt_hmask + 1] path hash | 1, 0 = empty
-  unsigned long long* wt_mask; // [2 * (wt_hmask + 1)] data / child masks
+  // [2 * (wt_hmask + 1)]: per entry the path hash | 1 (0 = empty) and the
+  // path's second hash | 1 (0 = not yet published), side by side
+  int64_t* wt_key;
+  // [2 * (wt_hmask + 1) + WT_STATS]: data / child masks, then the counters
+  // (WS_*: arms that found no entry)
+  unsigned long long* wt_mask;
   int64_t wt_hmask;
   // [ncap] per request of the batch being served: its parent node << 32 |
   // its SEQUENTIAL number, assigned in stream order by zk_tree_seq_order
@@ -311,7 +315,13 @@ int zk_watch_resume(const ZkTree*, const uint8_t*, const int64_t*,
 int64_t zk_tree_order_workspace(int64_t);
 int64_t zk_tree_order_stats_offset(int64_t);
 int zk_tree_expire(const ZkTree*, int64_t, int64_t, unsigned long long*,
-                   hipStream_t);
+                   int64_t*, int64_t, hipStream_t);
+// The watch table's maintenance (tree_watch.hip): clear watcher slot wslot's
+// bit from every mask; insert every entry of an old table (keys + tags,
+// masks, hmask) that has a non-zero mask into the tree's (zeroed) table.
+int zk_watch_drop(const ZkTree*, int32_t, hipStream_t);
+int zk_watch_rebuild(const ZkTree*, const int64_t*, const int64_t*, int64_t,
+                     hipStream_t);
 // SEQUENTIAL numbers of a batch in stream order (tree_seq.hip): bytes of
 // the workspace for ncap requests, the prefix of it that must be zero when
 // it is first used (the kernels leave it zero), and the ordering itself

@@ -656,33 +656,92 @@ ZK_DEV bool tree_erase_at(const ZkTree& t, int64_t s, int64_t v) {
 // ---- watches (one-shot, per watcher slot) ---------------------------------
 // A path-keyed table beside the tree (lib/zk-session.js:482-526 describes
 // the server semantics the client relies on): key = path
-// hash | 1 (0 = empty, linear probing, entries are never removed), two
-// 64-bit masks per entry — the data watches (GET_DATA / EXISTS with
-// watch=1; an EXISTS on a missing path is ZooKeeper's "exist" watch, kept
-// in the same set like the server's dataWatches) and the child watches —
-// one bit per watcher slot (<= 64 sessions of the server).  Firing is an
-// atomic exchange with 0: one-shot, and each watcher of a path is notified
-// exactly once even when several writes of a batch hit the path (the first
-// takes the mask).  Paths are keyed, not nodes, so a watch on a missing
-// path waits for its creation.
+// hash | 1 (0 = empty, linear probing, entries are removed only by the
+// rebuild, zk_watch_rebuild), two 64-bit masks per entry — the data watches
+// (GET_DATA / EXISTS with watch=1; an EXISTS on a missing path is
+// ZooKeeper's "exist" watch, kept in the same set like the server's
+// dataWatches) and the child watches — one bit per watcher slot (<= 64
+// sessions of the server).  Firing is an atomic exchange with 0: one-shot,
+// and each watcher of a path is notified exactly once even when several
+// writes of a batch hit the path (the first takes the mask).  Paths are
+// keyed, not nodes, so a watch on a missing path waits for its creation.
+//
+// Two paths of one key (hash twins) are told apart by a second word per
+// entry, tag = an independent 64-bit hash of the path | 1, folded in the
+// same pass over the bytes (path_hash2).  The claimer of a key publishes
+// its tag with atomicCAS(0 -> mine); nobody waits: an armer that reads 0
+// tries the same CAS (result 0 or mine: the entry is this path's, anything
+// else: a twin's, probe on), a fire that reads 0 treats the entry as an
+// insert of the launch it runs in and misses it, as the batch contract
+// allows.  Residual: two paths equal in BOTH 64-bit hashes (and in length,
+// which both fold) still alias; no path bytes are kept or compared.
 enum : int { WK_DATA = 0, WK_CHILD = 1 };
+// counters behind the masks (wt_mask[2 * (wt_hmask + 1) + WS_*])
+enum : int { WS_LOST = 0, WT_STATS = 8 };
 // notification types (lib/zk-consts.js NOTIFICATION_TYPE)
 enum : int32_t { NT_CREATED = 1, NT_DELETED = 2, NT_DATA_CHANGED = 3,
                  NT_CHILDREN_CHANGED = 4 };
 constexpr int WT_REC = 5;    // per request: m_path, m_path_child, m_parent,
                              // path word of the node, of its parent
 
-ZK_DEV int64_t wt_slot(const ZkTree& t, uint64_t key, bool insert) {
+// path_hash and the tag of the same bytes in one pass (other multipliers,
+// another seed: a pair built to collide in one does not in the other)
+ZK_DEV uint64_t path_hash2(const uint8_t* p, int32_t n, uint64_t* tag) {
+  uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)n;
+  uint64_t g = 0xD6E8FEB86659FD93ull + (uint64_t)n;
+  int32_t i = 0;
+  for (; i + 8 <= n; i += 8) {
+    uint64_t w; __builtin_memcpy(&w, p + i, 8);
+    h = (h ^ w) * 0xFF51AFD7ED558CCDull;
+    h ^= h >> 32;
+    g = (g + w) * 0x9FB21C651E98DF25ull;
+    g ^= g >> 29;
+  }
+  if (i < n) {
+    uint64_t w = 0;
+    for (int32_t k = 0; i + k < n; ++k) w |= (uint64_t)p[i + k] << (8 * k);
+    h = (h ^ w) * 0xFF51AFD7ED558CCDull;
+    h ^= h >> 32;
+    g = (g + w) * 0x9FB21C651E98DF25ull;
+    g ^= g >> 29;
+  }
+  h ^= h >> 33;
+  h *= 0xC4CEB9FE1A85EC53ull;
+  h ^= h >> 33;
+  g ^= g >> 31;
+  g *= 0xBF58476D1CE4E5B9ull;
+  g ^= g >> 30;
+  *tag = g | 1ull;
+  return h;
+}
+
+// (key and tag side by side: the second word of a probe is in the line the
+// first one fetched)
+ZK_DEV int64_t* wt_tag(const ZkTree& t, int64_t s) {
+  return &t.wt_key[2 * s + 1];
+}
+
+ZK_DEV int64_t wt_slot(const ZkTree& t, uint64_t key, uint64_t tag,
+                       bool insert) {
   int64_t s = (int64_t)key & t.wt_hmask;
   for (int64_t probe = 0; probe <= t.wt_hmask; ++probe) {
-    int64_t k = __hip_atomic_load(&t.wt_key[s], __ATOMIC_RELAXED,
+    int64_t k = __hip_atomic_load(&t.wt_key[2 * s], __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT);
-    if (k == (int64_t)key) return s;
     if (k == 0) {
       if (!insert) return -1;
-      k = (int64_t)atomicCAS((unsigned long long*)&t.wt_key[s], 0ull,
+      k = (int64_t)atomicCAS((unsigned long long*)&t.wt_key[2 * s], 0ull,
                              (unsigned long long)key);
-      if (k == 0 || k == (int64_t)key) return s;
+      if (k == 0) k = (int64_t)key;
+    }
+    if (k == (int64_t)key) {
+      int64_t g = __hip_atomic_load(wt_tag(t, s), __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+      if (g == 0 && insert) {
+        g = (int64_t)atomicCAS((unsigned long long*)wt_tag(t, s), 0ull,
+                               (unsigned long long)tag);
+        if (g == 0) g = (int64_t)tag;
+      }
+      if (g == (int64_t)tag) return s;
     }
     s = (s + 1) & t.wt_hmask;
   }
@@ -692,19 +751,33 @@ ZK_DEV int64_t wt_slot(const ZkTree& t, uint64_t key, bool insert) {
 ZK_DEV void wt_arm(const ZkTree& t, const uint8_t* p, int32_t n, int kind,
                    int32_t wslot) {
   if (t.wt_key == nullptr || wslot < 0 || wslot > 63) return;
-  const int64_t s = wt_slot(t, path_hash(p, n) | 1ull, true);
+  uint64_t tag;
+  const uint64_t key = path_hash2(p, n, &tag) | 1ull;
+  const int64_t s = wt_slot(t, key, tag, true);
   if (s >= 0) atomicOr(&t.wt_mask[2 * s + kind], 1ull << wslot);
+  else atomicAdd(&t.wt_mask[2 * (t.wt_hmask + 1) + WS_LOST], 1ull);
 }
 
-ZK_DEV uint64_t wt_fire(const ZkTree& t, const uint8_t* p, int32_t n,
-                        int kind) {
-  if (t.wt_key == nullptr) return 0;
-  const int64_t s = wt_slot(t, path_hash(p, n) | 1ull, false);
+// The entry of a path for wt_fire_at (-1: none): one probe for a write that
+// fires both of a path's masks.
+ZK_DEV int64_t wt_find(const ZkTree& t, const uint8_t* p, int32_t n) {
+  if (t.wt_key == nullptr) return -1;
+  uint64_t tag;
+  const uint64_t key = path_hash2(p, n, &tag) | 1ull;
+  return wt_slot(t, key, tag, false);
+}
+
+ZK_DEV uint64_t wt_fire_at(const ZkTree& t, int64_t s, int kind) {
   if (s < 0) return 0;
   unsigned long long* m = &t.wt_mask[2 * s + kind];
   if (__hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
     return 0;
   return atomicExch(m, 0ull);
+}
+
+ZK_DEV uint64_t wt_fire(const ZkTree& t, const uint8_t* p, int32_t n,
+                        int kind) {
+  return wt_fire_at(t, wt_find(t, p, n), kind);
 }
 
 // Node v's path from its path word.

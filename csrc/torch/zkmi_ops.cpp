@@ -108,7 +108,8 @@ ZkNodeStore node_store(const std::vector<Tensor>& v, size_t at,
 // [ht, node_path_off, node_path_len, node_parent, path_arena, counters,
 //  slab, slot_off, data_len, slot_cap, free_list, cn, pzxid, dirty,
 //  dirty_list, node_pw, node_path_cap, eph] + optionally [wt_key, wt_mask]
-//  (watches); sizes give mask, caps
+//  (watches: 2 h key / tag words, 2 h masks + 8 counters); sizes give mask,
+//  caps
 ZkTree tree(const std::vector<Tensor>& v) {
   TORCH_CHECK(v.size() == 18 || v.size() == 20,
               "zkmi: tree needs 18 tensors (20 with a watch table), got ",
@@ -145,12 +146,14 @@ ZkTree tree(const std::vector<Tensor>& v) {
   t.wt_mask = nullptr;
   t.wt_hmask = 0;
   if (v.size() == 20) {
-    const int64_t h = v[18].numel();
-    TORCH_CHECK(h > 0 && (h & (h - 1)) == 0,
-                "zkmi: tree.wt_key must hold a power of two of entries");
-    t.wt_key = P<int64_t>(v[18], I64, h, "tree.wt_key", r);
+    // {key, tag} pairs; masks then the WT_STATS (8) counters (zk_tree.h)
+    const int64_t h = v[18].numel() / 2;
+    TORCH_CHECK(h >= 8 && (h & (h - 1)) == 0 && v[18].numel() == 2 * h,
+                "zkmi: tree.wt_key must hold a power of two of entries, "
+                "two words each");
+    t.wt_key = P<int64_t>(v[18], I64, 2 * h, "tree.wt_key", r);
     t.wt_mask = reinterpret_cast<unsigned long long*>(
-        P<int64_t>(v[19], I64, 2 * h, "tree.wt_mask", r));
+        P<int64_t>(v[19], I64, 2 * h + 8, "tree.wt_mask", r));
     t.wt_hmask = h - 1;
   }
   t.seqno = nullptr;
@@ -875,8 +878,34 @@ void watch_resume(const std::vector<Tensor>& t, const Tensor& rx,
              P<int32_t>(ev_type, I32, cap, "ev_type", d),
              P<int64_t>(ev_poff, I64, cap, "ev_path_off", d),
              P<int32_t>(ev_plen, I32, cap, "ev_path_len", d),
-             P<int64_t>(out, I64, 3, "out", d), cur_stream()),
+             P<int64_t>(out, I64, 4, "out", d), cur_stream()),
          "watch_resume");
+}
+
+// Clear watcher slot wslot's bit from every mask of the tree's watch table.
+void watch_drop(const std::vector<Tensor>& t, int64_t wslot) {
+  ZkTree s = tree(t);
+  TORCH_CHECK(s.wt_key != nullptr, "zkmi: watch_drop needs a watch table");
+  TORCH_CHECK(wslot >= 0 && wslot < 64, "zkmi: watcher slot 0..63");
+  hip_ok(zk_watch_drop(&s, (int32_t)wslot, cur_stream()), "watch_drop");
+}
+
+// The entries of an old watch table (its key and mask tensors) that still
+// hold a watch, inserted into the tree's new, zeroed one.
+void watch_rebuild(const std::vector<Tensor>& t, const Tensor& okey,
+                   const Tensor& omask) {
+  ZkTree s = tree(t);
+  TORCH_CHECK(s.wt_key != nullptr, "zkmi: watch_rebuild needs a watch table");
+  const int64_t h = okey.numel() / 2;
+  TORCH_CHECK(h >= 8 && (h & (h - 1)) == 0 && okey.numel() == 2 * h,
+              "zkmi: the old wt_key must hold a power of two of entries");
+  const Tensor* d = &t[0];
+  const int64_t* ok = P<int64_t>(okey, I64, 2 * h, "old wt_key", d);
+  TORCH_CHECK(ok != s.wt_key, "zkmi: watch_rebuild into the same table");
+  hip_ok(zk_watch_rebuild(&s, ok,
+                          P<int64_t>(omask, I64, 2 * h + 8, "old wt_mask", d),
+                          h - 1, cur_stream()),
+         "watch_rebuild");
 }
 
 // SEQUENTIAL numbers in stream order (tree_seq.hip): workspace bytes for
@@ -1146,14 +1175,21 @@ void tree_mix_merge(const Tensor& cls, const Tensor& sub, const Tensor& n_dev,
          "tree_mix_merge");
 }
 
+// rec (a tree with a watch table): [records wanted (the caller zeroes it), 7
+// unused, 5 words a record] for the watches the removals fired.
 void tree_expire(const std::vector<Tensor>& t, int64_t session, int64_t ncap,
-                 const Tensor& removed) {
+                 const Tensor& removed, const c10::optional<Tensor>& rec,
+                 int64_t rec_cap) {
   ZkTree s = tree(t);
   TORCH_CHECK(ncap <= s.store.cap, "zkmi: tree_expire range");
+  TORCH_CHECK(!rec.has_value() || (s.wt_key != nullptr && rec_cap >= 0),
+              "zkmi: tree_expire records need a watch table");
+  int64_t* rp = rec.has_value()
+      ? P<int64_t>(*rec, I64, 8 + 5 * rec_cap, "rec", &t[0]) : nullptr;
   hip_ok(zk_tree_expire(&s, session, ncap,
                         reinterpret_cast<unsigned long long*>(P<int64_t>(
                             removed, I64, 1, "removed", &t[0])),
-                        cur_stream()),
+                        rp, rec_cap, cur_stream()),
          "tree_expire");
 }
 
@@ -1570,8 +1606,12 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor frame_len, Tensor count, int ncap, int wslot, "
         "Tensor(b!) ent, Tensor(c!) ev_type, Tensor(d!) ev_path_off, "
         "Tensor(e!) ev_path_len, Tensor(f!) out) -> ()", &watch_resume);
+  m.def("watch_drop(Tensor(a!)[] tree, int wslot) -> ()", &watch_drop);
+  m.def("watch_rebuild(Tensor(a!)[] tree, Tensor old_key, Tensor old_mask) "
+        "-> ()", &watch_rebuild);
   m.def("tree_expire(Tensor(a!)[] tree, int session, int ncap, "
-        "Tensor(b!) removed) -> ()", &tree_expire);
+        "Tensor(b!) removed, Tensor(c!)? rec=None, int rec_cap=0) -> ()",
+        &tree_expire);
   m.def("bench_gen_get(int n, int seed, int leaf0, int nleaves, "
         "int xid_base, Tensor node_pw, Tensor(a!) idx, Tensor(b!) xid, "
         "Tensor(c!) path_off, Tensor(d!) path_len, Tensor? state=None, "

@@ -16,7 +16,8 @@ OPS = ('scan_excl', 'encode_requests', 'encode_set_watches',
        'encode_connect_requests', 'encode_responses', 'frame_scan',
        'decode_replies', 'expand_strings', 'expand_acl', 'decode_requests',
        'decode_connect_responses', 'tree_fill', 'tree_build', 'tree_serve',
-       'tree_expire', 'bench_gen_get', 'bench_check_get',
+       'tree_expire', 'watch_events', 'watch_resume', 'watch_drop',
+       'watch_rebuild', 'bench_gen_get', 'bench_check_get',
        'bench_check_notif', 'route_requests', 'session_connect',
        'session_close')
 

@@ -350,12 +350,15 @@ class TreeModel(object):
             del self.zx[path]
             self.dead.add(path)
         self.db.expire_session(sid)
-        removed = int(self.tree.expire(sid).item())
+        removed = self._expire_on_gpu(sid)
         assert removed == len(gone)
         assert self.counter(_lib.TC_ZXID) == z
         if audit:
             self.audit()
         return removed
+
+    def _expire_on_gpu(self, sid):
+        return int(self.tree.expire(sid).item())
 
     # -- the audit ------------------------------------------------------------
 

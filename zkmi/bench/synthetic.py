@@ -233,9 +233,8 @@ class GpuTree(object):
         # tree with one fires the watches its writes hit
         self.watch = None
         if watch_cap > 0:
-            wh = _next_pow2(2 * int(watch_cap))
-            self.watch = (torch.zeros(wh, dtype=I64, device=dev),
-                          torch.zeros(2 * wh, dtype=I64, device=dev))
+            self.watch = self._watch_table(
+                max(_next_pow2(2 * int(watch_cap)), 8))
             self._tensors = self._tensors + list(self.watch)
         # ACL table (acl_cap > 0: room for that many distinct ACLs beside the
         # open one): csrc/kernels/tree_acl.hip.  A server over a tree with
@@ -304,14 +303,75 @@ class GpuTree(object):
         raw = bytes(self.acl[1][off:off + ln].cpu().numpy().tobytes())
         return jute.JuteReader(raw, 0).read_acl()
 
-    def expire(self, session, removed=None):
+    def _watch_table(self, wh):
+        """The tensors of an empty watch table of ``wh`` entries (zk_abi.h
+        ZkTree wt_key / wt_mask): per entry the key and the second hash
+        word; the data / child masks and then the counter words."""
+        dev = self.device
+        return (torch.zeros(2 * wh, dtype=I64, device=dev),
+                torch.zeros(2 * wh + _lib.WT_STATS, dtype=I64, device=dev))
+
+    @property
+    def watch_hcap(self):
+        """Entries of the watch table."""
+        return self.watch[0].numel() // 2
+
+    def expire(self, session, removed=None, rec=None):
         """Delete every ephemeral node owned by ``session`` (server side of
         session expiry).  ``removed`` (device int64 [1]) accumulates the
-        number of nodes removed."""
+        number of nodes removed.
+
+        On a tree with a watch table every removal fires what a DELETE
+        fires (the node's data and child watches, its parent's child
+        watches).  ``rec`` (device int64 [8 + 5 * k]) takes one record per
+        removal that fired a watch, for k of them, and in ``rec[0]`` the
+        number wanted: :meth:`GpuServer.expire` turns them into
+        notifications.  Without it the fired watches are consumed and
+        nobody is told."""
         if removed is None:
             removed = torch.zeros(1, dtype=I64, device=self.device)
-        _lib.lib().tree_expire(self._tensors, session, self.cap, removed)
+        if rec is None:
+            _lib.lib().tree_expire(self._tensors, session, self.cap, removed)
+        else:
+            rec[0:1].zero_()
+            _lib.lib().tree_expire(self._tensors, session, self.cap, removed,
+                                   rec, (rec.numel() - 8) // 5)
         return removed
+
+    def watch_drop(self, wslot):
+        """Clear watcher slot ``wslot``'s bit from every mask of the watch
+        table: a closed or expired session's watches go with it (ZooKeeper
+        keeps them on the connection), so nothing of it fires into the next
+        session bound to the slot."""
+        if self.watch is None:
+            raise ValueError('watch_drop: the tree keeps no watch table')
+        _lib.lib().watch_drop(self._tensors, int(wslot))
+
+    def watch_rehash(self, watch_cap=None):
+        """Rebuild the watch table from the entries that still hold a watch
+        (a fire empties an entry's masks but leaves the entry, so every path
+        ever watched takes one until this runs), into a table for
+        ``watch_cap`` watched paths (default: the size it has).  The lost-arm
+        count carries over.  Any server over the tree sees the new table at
+        once (the descriptor list is updated in place)."""
+        if self.watch is None:
+            raise ValueError('watch_rehash: the tree keeps no watch table')
+        wh = self.watch_hcap if watch_cap is None else \
+            max(_next_pow2(2 * int(watch_cap)), 8)
+        old = self.watch
+        self.watch = self._watch_table(wh)
+        self._tensors[18:20] = list(self.watch)
+        _lib.lib().watch_rebuild(self._tensors, old[0], old[1])
+
+    def watch_census(self):
+        """(entries in use, entries holding a watch, arms lost to a full
+        table) of the watch table.  One host read."""
+        wh = self.watch_hcap
+        key = self.watch[0][0:2 * wh:2]
+        m = self.watch[1][:2 * wh].view(wh, 2)
+        held = ((m[:, 0] | m[:, 1]) != 0)
+        return (int((key != 0).sum().item()), int(held.sum().item()),
+                int(self.watch[1][2 * wh + _lib.WS_LOST].item()))
 
     def rehash(self):
         """Rebuild the hash index from the live nodes (drops tombstones left
@@ -501,7 +561,11 @@ class GpuServer(object):
         self.ev_plen = torch.empty(ecap, dtype=I32, device=dev)
         # [events written (<= ecap), events fired]
         self.ev_total = torch.zeros(2, dtype=I64, device=dev)
-        self.rs_out = torch.zeros(3, dtype=I64, device=dev)
+        # [events written, re-armed, events, listed paths dropped]
+        self.rs_out = torch.zeros(4, dtype=I64, device=dev)
+        self.notif_err = None             # K13's error flag of the last
+        self.resume_err = None            # notification / catch-up encode
+        self.exp_rec = None               # expiry records (lazy)
         # notification frame: 4 + 16 header + type + state + path
         self.maxpath = int(self.tree.node_path_len.max().item()) + 16
         self.notif_buf = torch.empty(ecap * (28 + 4 + self.maxpath) + 64,
@@ -523,21 +587,91 @@ class GpuServer(object):
             torch.full((cap,), -1, dtype=I64, device=dev),
             poff, plen, arena, ntype, count)
 
-    def _notify(self):
-        """Expand the fired masks of the last serve into events (request
-        order) and encode them: ``self.notif = (stream, bytes, slot per
-        frame, events)`` — the watchers' notification frames, all on the
-        device."""
+    def _notify(self, op=None, err=None, count=None, fired=None):
+        """Expand the fired masks of the last serve (or the records of an
+        expiry: ``op`` .. ``fired``) into events (request order) and encode
+        them: ``self.notif = (stream, bytes, slot per frame, events)`` — the
+        watchers' notification frames, all on the device.  Events past
+        ``self.ecap`` are not written (their watches are spent all the
+        same) and the encoder's error flag is kept: :meth:`watch_stats`
+        reports both."""
         L = _lib.lib()
-        r = self.resp
-        L.watch_events(r.opcode, r.err, r.count, self.cap_frames, self.fired,
+        if op is None:
+            r = self.resp
+            op, err, count, fired = r.opcode, r.err, r.count, self.fired
+        L.watch_events(op, err, count, self.cap_frames, fired,
                        self.wbsum, self.ev_slot, self.ev_type, self.ev_poff,
                        self.ev_plen, self.ev_total)
-        out, rec_off, total, _ = B.encode_responses(
+        out, rec_off, total, nerr = B.encode_responses(
             self._nresp, self.tree.store, self.notif_buf.numel(),
             out=self.notif_buf)
         self.notif_rec_off = rec_off
+        self.notif_err = nerr
         self.notif = (out, total, self.ev_slot, self.ev_total[0:1])
+
+    def expire(self, session, wslot=None, removed=None):
+        """Expire ``session``: its ephemerals are removed as one txn
+        (:meth:`GpuTree.expire`) and, on a tree with a watch table, the
+        watches the removals fire become ``self.notif`` as a served batch's
+        do (NodeDeleted to the data and child watchers of each removed node,
+        one a watcher; NodeChildrenChanged to its parent's), in no
+        particular order.  ``wslot``: the expired session's watcher slot;
+        its own watches are dropped first (:meth:`GpuTree.watch_drop`), as
+        ZooKeeper drops a closed session's, so it is told nothing and the
+        slot's next session inherits nothing.  Returns ``removed``.
+
+        Room for ``cap_frames`` removals that fire a watch; more are counted
+        in :meth:`watch_stats` and their events lost."""
+        tree = self.tree
+        if tree.watch is None:
+            return tree.expire(session, removed)
+        dev = tree.device
+        if wslot is not None:
+            tree.watch_drop(wslot)
+        if self.exp_rec is None:
+            cap = self.cap_frames
+            self.exp_rec = torch.zeros(8 + 5 * cap, dtype=I64, device=dev)
+            self.exp_op = torch.full((cap,), consts.OP_CODES['DELETE'],
+                                     dtype=I32, device=dev)
+            self.exp_err = torch.zeros(cap, dtype=I32, device=dev)
+        removed = tree.expire(session, removed, rec=self.exp_rec)
+        self._notify(self.exp_op, self.exp_err, self.exp_rec[0:1],
+                     self.exp_rec[8:])
+        return removed
+
+    def watch_stats(self):
+        """The watch path's loss counters (one host read), all 0 on a
+        server that lost nothing:
+
+        ``lost_arms``       watches that found no entry in a full table since
+                            the tree was built (:meth:`GpuTree.watch_rehash`
+                            is the remedy); their watchers will not be told
+        ``events_fired``,   of the last serve / expiry: more fired than
+        ``events_written``  written means ``ecap`` overflowed and the rest
+                            were dropped, their watches spent
+        ``encode_err``      the notification encoder's error flag of the last
+                            serve / expiry (2: ``notif_buf`` too small)
+        ``expiry_dropped``  removals of the last :meth:`expire` whose fired
+                            watches found no record
+        ``resume_dropped``, paths of the last SET_WATCHES catch-up that were
+        ``resume_err``      neither answered nor re-armed; its encoder's flag
+        """
+        wh = self.tree.watch_hcap
+        ev = self.ev_total.cpu().tolist()
+        st = {'lost_arms':
+              int(self.tree.watch[1][2 * wh + _lib.WS_LOST].item()),
+              'events_fired': ev[1], 'events_written': ev[0],
+              'encode_err': 0 if self.notif_err is None
+              else int(self.notif_err.item()),
+              'expiry_dropped': 0, 'resume_dropped': 0, 'resume_err': 0}
+        if self.exp_rec is not None:
+            st['expiry_dropped'] = max(
+                0, int(self.exp_rec[0].item()) - self.cap_frames)
+        if self.resume_err is not None:
+            rs = self.rs_out.cpu().tolist()
+            st['resume_dropped'] = rs[3] + rs[2] - rs[0]
+            st['resume_err'] = int(self.resume_err.item())
+        return st
 
     def _resume(self, rx, ft, wslot):
         """SET_WATCHES catch-up of the batch's SET_WATCHES frames for
@@ -546,7 +680,9 @@ class GpuServer(object):
         arena; the other watches are re-armed."""
         L = _lib.lib()
         dev = self.tree.device
-        cap = self.ecap
+        # a listed path takes at least the 4 bytes of its length in its
+        # frame: no list of this stream is longer than its bytes / 4
+        cap = max(self.ecap, int(rx.numel()) // 4)
         ev_type = torch.empty(cap, dtype=I32, device=dev)
         ev_poff = torch.empty(cap, dtype=I64, device=dev)
         ev_plen = torch.empty(cap, dtype=I32, device=dev)
@@ -559,8 +695,9 @@ class GpuServer(object):
         # paths of a SET_WATCHES are bounded by its frame: ZooKeeper paths
         buf = torch.empty(cap * 32 + int(rx.numel()) + 64, dtype=U8,
                           device=dev)
-        out, _, total, _ = B.encode_responses(nb, self.tree.store,
-                                              buf.numel(), out=buf)
+        out, _, total, rerr = B.encode_responses(nb, self.tree.store,
+                                                 buf.numel(), out=buf)
+        self.resume_err = rerr
         self.resume_notif = (out, total, self.rs_out)
 
     def serve(self, rx, n, session=0, terminate=False, ordered=False,

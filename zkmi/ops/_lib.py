@@ -39,6 +39,8 @@ TC_SESS, TC_N = 8, 9
 # serve / expire `session` argument: the one in counters[TC_SESS]
 SESS_DEV = -2
 HT_WORDS = 8     # int64 words per hash entry: key, val, lengths, path head
+# watch table (zk_tree.h): counter words behind the masks, the lost-arm one
+WT_STATS, WS_LOST = 8, 0
 
 SCAN_SHFL, SCAN_MFMA, SCAN_MFMA_W1, SCAN_MFMA_W4 = 0, 1, 2, 3
 SCAN_MFMA_FORCE = 4      # the multi-block MFMA path at any n (tests)
