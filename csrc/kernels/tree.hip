@@ -4,7 +4,8 @@
 // launchers stand below its kernels.  The other passes have a file each:
 // tree_order.hip (in-batch ordering and the ordered serve), tree_seq.hip
 // (SEQUENTIAL numbering), tree_list.hip (GET_CHILDREN*), tree_watch.hip
-// (watch events and the SET_WATCHES catch-up).
+// (watch events and the SET_WATCHES catch-up), tree_acl.hip, tree_mix.hip,
+// tree_snap.hip (the image: snapshot and load).
 #include "zk_tree.h"
 #include "zk_frame_rows.h"
 
@@ -1053,6 +1054,14 @@ __global__ __launch_bounds__(TR_T) void ht_census_k(
     atomicAdd(&out[2], (unsigned long long)used);
     atomicAdd(&out[3], (unsigned long long)tomb);
   }
+}
+
+int digest_launch(const ZkTree* t, unsigned long long* out, hipStream_t st) {
+  const int64_t nb = (t->store.cap + TR_T - 1) / TR_T;
+  if (nb <= 0) return 0;
+  tree_digest_k<<<(unsigned)nb, TR_T, 0, st>>>(*t, out);
+  ZK_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace zk

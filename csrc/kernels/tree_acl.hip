@@ -1,7 +1,7 @@
 // The GPU tree's ACL path: the ACL store beside the tree (ZkAclTable,
 // zk_abi.h), the pass that records a batch's CREATE ACLs and the GET_ACL
 // serve (the tree: zk_tree.h).
-#include "zk_tree.h"
+#include "zk_acl.h"
 
 namespace zk {
 
@@ -11,29 +11,7 @@ namespace zk {
 // CREATE request), so a GET_ACL reply copies it.  Every vector is stored
 // once: an open-addressing index (key = 64-bit content hash | 1, val = the
 // arena word) interns them at create time; the read path never touches it.
-// ACL_LOST: the store had no room for the vector (full index, full arena,
-// the entry limit, or two new vectors of one batch with one hash); a GET_ACL
-// on such a node answers SYSTEMERROR.  Nothing is ever reclaimed.
-constexpr int64_t ACL_LOST = -1;
-constexpr int64_t ACL_LEN_MAX = 1 << 24;
-// ctr[]: arena top (a bump allocator: a claim that does not fit stays added,
-// so the arena then counts as full), entries, nodes bound lost, the arena
-// top when the last record pass ended, the entry limit (set by the owner)
-enum : int { AC_TOP = 0, AC_ENT = 1, AC_LOST = 2, AC_OLD_TOP = 3,
-             AC_LIMIT = 4 };
-// per request of a record pass: the index slot its vector landed on
-constexpr int32_t AS_NONE = -2;                // not a successful CREATE
-constexpr int32_t AS_LOST = -1;                // no slot
-
-ZK_DEV int64_t acl_off(int64_t w) { return w >> 24; }
-ZK_DEV int32_t acl_len(int64_t w) { return (int32_t)(w & 0xFFFFFF); }
-// a word that names bytes inside the arena (anything else reads as lost)
-ZK_DEV bool acl_word_ok(const ZkAclTable& a, int64_t w) {
-  return w > 0 && acl_len(w) >= 4 && acl_off(w) + acl_len(w) <= a.arena_cap;
-}
-ZK_DEV int64_t ld_relaxed(const int64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// The words and counters: zk_acl.h.
 
 // One workspace for both passes (they run one after the other on a stream).
 struct AclWs {

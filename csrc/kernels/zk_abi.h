@@ -385,6 +385,22 @@ int zk_tree_mix_merge(const int32_t*, const int32_t*, const int64_t*,
                       const int64_t* const*, const int32_t* const*, uint8_t*,
                       int64_t, uint8_t*, int64_t, int64_t*, int64_t*, int32_t*,
                       int32_t, hipStream_t);
+// The tree image (tree_snap.hip; layout and outcome codes: zk_snap.h).  a:
+// the tree's ACL table or null.  Snapshot: workspace bytes for a node
+// capacity; zk_tree_snap_size sizes the image on ws (total[0] = image bytes,
+// total[1] = records), zk_tree_snap_write then writes it into out[0, out_cap)
+// (status[0] = SNAP_OK or SNAP_NO_ROOM, status[1] = -1).  Load: workspace
+// bytes for n records; (image + bytes, n as the host read it, data capacity,
+// workspace + bytes, status[2] = SNAP_* and the record index) into a fresh,
+// empty tree.  None makes a host read.
+int64_t zk_tree_snap_workspace(int64_t cap);
+int64_t zk_tree_load_workspace(int64_t n);
+int zk_tree_snap_size(const ZkTree*, const ZkAclTable*, uint8_t*, int64_t,
+                      int64_t*, hipStream_t);
+int zk_tree_snap_write(const ZkTree*, const ZkAclTable*, uint8_t*, int64_t,
+                       uint8_t*, int64_t, int64_t*, hipStream_t);
+int zk_tree_load(const ZkTree*, const ZkAclTable*, const uint8_t*, int64_t,
+                 int64_t, int32_t, uint8_t*, int64_t, int64_t*, hipStream_t);
 int zk_bench_gen_get(int64_t, uint64_t, int64_t, int64_t, int32_t,
                      const int64_t*, int64_t*, int32_t*, int64_t*, int32_t*,
                      const int64_t*, int64_t*, int64_t*, hipStream_t);

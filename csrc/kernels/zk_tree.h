@@ -47,7 +47,7 @@
 // (all __forceinline__ device code), and at its end the few host functions
 // through which one file launches another's kernel.  The kernels and their
 // launchers: tree.hip, tree_order.hip, tree_seq.hip, tree_list.hip,
-// tree_watch.hip.
+// tree_watch.hip, tree_acl.hip, tree_mix.hip, tree_snap.hip.
 #pragma once
 #include "zk_common.h"
 
@@ -847,7 +847,7 @@ ZK_DEV void wave_mark_dirty_at(const ZkTree& t, int64_t par, int32_t flag) {
 
 // ---- host side: launches shared by the tree's files -------------------------
 // A kernel is launched from the file that defines it (the build has no
-// relocatable device code); the other tree files reach these three through
+// relocatable device code); the other tree files reach these four through
 // plain host functions.
 
 // One tree_serve_k launch (tree.hip).  The requests are K12's table (q), or,
@@ -883,6 +883,10 @@ int serve_launch(const ServeLaunch& s, hipStream_t st);
 // bump when n_dev is null.
 int finish_launch(const ZkTree* t, const int64_t* n_dev, int64_t bump,
                   int32_t publish, hipStream_t st);
+
+// tree_digest_k alone (tree.hip): out[0] += the digest sum of the live nodes,
+// out[1] += their number (the caller zeroes them); no census of the index.
+int digest_launch(const ZkTree* t, unsigned long long* out, hipStream_t st);
 
 // ord_bscan_k (tree_order.hip): bsum[0, nb) -> its exclusive prefix, in place.
 int bscan_launch(int64_t* bsum, int64_t nb, hipStream_t st);

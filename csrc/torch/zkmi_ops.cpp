@@ -976,6 +976,90 @@ void tree_digest(const std::vector<Tensor>& t, const Tensor& out) {
          "tree_digest");
 }
 
+// The tree image (tree_snap.hip).  acl: the ACL table's tensor list, or an
+// empty list for a tree without one.
+int64_t tree_snap_workspace(int64_t cap) {
+  TORCH_CHECK(cap >= 0, "zkmi: tree_snap_workspace cap");
+  return zk_tree_snap_workspace(cap);
+}
+
+int64_t tree_load_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_load_workspace n");
+  return zk_tree_load_workspace(n);
+}
+
+uint8_t* snap_ws(const Tensor& ws, int64_t bytes, const Tensor* d) {
+  uint8_t* w = P<uint8_t>(ws, U8, bytes, "image workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w) % 16 == 0,
+              "zkmi: image workspace must be 16-byte aligned");
+  return w;
+}
+
+// Size the image of the tree on ws: total (int64 [2]) = image bytes, records.
+void tree_snap_size(const std::vector<Tensor>& t,
+                    const std::vector<Tensor>& acl, const Tensor& ws,
+                    const Tensor& total) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a;
+  if (!acl.empty()) a = acl_table(acl, d);
+  hip_ok(zk_tree_snap_size(
+             &s, acl.empty() ? nullptr : &a,
+             snap_ws(ws, zk_tree_snap_workspace(s.store.cap), d), ws.numel(),
+             P<int64_t>(total, I64, 2, "total", d), cur_stream()),
+         "tree_snap_size");
+}
+
+// Write the image sized on ws into out[:out_cap]; status (int64 [2]).
+void tree_snap_write(const std::vector<Tensor>& t,
+                     const std::vector<Tensor>& acl, const Tensor& ws,
+                     const Tensor& out, int64_t out_cap,
+                     const Tensor& status) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a;
+  if (!acl.empty()) a = acl_table(acl, d);
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_snap_write out_cap");
+  uint8_t* o = P<uint8_t>(out, U8, out_cap, "out", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0,
+              "zkmi: the image buffer must be 16-byte aligned");
+  hip_ok(zk_tree_snap_write(
+             &s, acl.empty() ? nullptr : &a,
+             snap_ws(ws, zk_tree_snap_workspace(s.store.cap), d), ws.numel(),
+             o, out_cap, P<int64_t>(status, I64, 2, "status", d),
+             cur_stream()),
+         "tree_snap_write");
+}
+
+// Load image[:image_len] of n records into the fresh tree; status (int64 [2]).
+void tree_load(const std::vector<Tensor>& t, const std::vector<Tensor>& acl,
+               const Tensor& image, int64_t image_len, int64_t n,
+               int64_t data_cap, const Tensor& ws, const Tensor& status) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a;
+  if (!acl.empty()) {
+    a = acl_table(acl, d);
+    TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+                " elements, needs ", s.store.cap);
+  }
+  TORCH_CHECK(image_len >= 0, "zkmi: tree_load image_len");
+  TORCH_CHECK(n >= 0 && n < (1ll << 31) - 1, "zkmi: tree_load n");
+  TORCH_CHECK(n == 0 || 64 + 8 * (n + 1) <= image_len,
+              "zkmi: tree_load: the table of ", n,
+              " records does not fit the image");
+  TORCH_CHECK(data_cap >= 0 && data_cap < (1ll << 24),
+              "zkmi: tree_load data_cap");
+  hip_ok(zk_tree_load(
+             &s, acl.empty() ? nullptr : &a,
+             P<uint8_t>(image, U8, std::max<int64_t>(image_len, 1), "image",
+                        d),
+             image_len, n, (int32_t)data_cap,
+             snap_ws(ws, zk_tree_load_workspace(n), d), ws.numel(),
+             P<int64_t>(status, I64, 2, "status", d), cur_stream()),
+         "tree_load");
+}
+
 // GET_CHILDREN / GET_CHILDREN2 batches served from the tree
 // (tree_list.hip): workspace bytes for ncap requests, then per batch the request
 // frames -> the framed replies in out[:total], their starts in rec_off.
@@ -1568,6 +1652,18 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor frame_len, Tensor count, int ncap, Tensor(b!) ws, "
         "Tensor(c!) seqno) -> ()", &tree_seq_order);
   m.def("tree_digest(Tensor[] tree, Tensor(a!) out) -> ()", &tree_digest);
+  m.def("tree_snap_workspace(int cap) -> int", &tree_snap_workspace);
+  m.def("tree_load_workspace(int n) -> int", &tree_load_workspace);
+  m.def("tree_snap_size(Tensor[] tree, Tensor[] acl, Tensor(a!) ws, "
+        "Tensor(b!) total) -> ()",
+        &tree_snap_size);
+  m.def("tree_snap_write(Tensor[] tree, Tensor[] acl, Tensor(a!) ws, "
+        "Tensor(b!) out, int out_cap, Tensor(c!) status) -> ()",
+        &tree_snap_write);
+  m.def("tree_load(Tensor(a!)[] tree, Tensor(b!)[] acl, Tensor image, "
+        "int image_len, int n, int data_cap, Tensor(c!) ws, "
+        "Tensor(d!) status) -> ()",
+        &tree_load);
   m.def("tree_list_workspace(int n) -> int", &tree_list_workspace);
   m.def("tree_list(Tensor(a!)[] tree, Tensor rx, Tensor frame_off, "
         "Tensor frame_len, Tensor count, int ncap, int wslot, int max_frame, "

@@ -136,60 +136,98 @@ class GpuTree(object):
         self.data_bytes = data_bytes
         self.data_dist = data_dist
         cap = int(nst * (1 + spare)) + 1024
-        self.cap = cap
         enc = [p.encode() for p in paths]
         plen = np.fromiter((len(e) for e in enc), np.int32, nst)
         poff = np.zeros(nst, np.int64)
         np.cumsum(plen[:-1], out=poff[1:])
         arena = b''.join(enc)
-        # every spare node may need a fresh path (up to 64 bytes each, in
-        # 16-byte multiples)
-        self.path_cap = len(arena) + (cap - nst) * 80 + (1 << 16)
-        self.path_arena = torch.zeros(self.path_cap, dtype=U8, device=dev)
-        self.path_arena[:len(arena)] = torch.frombuffer(
-            bytearray(arena), dtype=U8).to(dev)
-        self.node_path_off = torch.zeros(cap, dtype=I64, device=dev)
-        self.node_path_len = torch.zeros(cap, dtype=I32, device=dev)
-        self.node_path_off[:nst] = torch.from_numpy(poff).to(dev)
-        self.node_path_len[:nst] = torch.from_numpy(plen).to(dev)
-        # bytes of each node's path storage (the static paths are packed)
-        self.node_path_cap = torch.zeros(cap, dtype=I32, device=dev)
-        self.node_path_cap[:nst] = self.node_path_len[:nst]
-        # path word (offset << 24 | length) the hash lookups verify against
-        self.node_pw = torch.zeros(cap, dtype=I64, device=dev)
-        self.node_pw[:nst] = torch.from_numpy(
-            (poff << 24) | plen.astype(np.int64)).to(dev)
-        self.node_parent = torch.full((cap,), -1, dtype=I64, device=dev)
-        self.node_parent[:nst] = torch.from_numpy(parents).to(dev)
         # wire-format slots; data capacity >= 128 so sets can grow
         dcap = max(data_bytes, 128)
         sb = slot_bytes(dcap)
-        self.slot = sb
-        self.slab_cap = cap * sb
-        # hash vals pack node (32 bits) and slot offset / 16 (31 bits)
-        assert cap < (1 << 31) and self.slab_cap < (1 << 35), 'tree too big'
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
-        # scratch: bytes past the tree's slab for the snapshots of ordered
-        # serving (GpuServer.serve(ordered=True)); the tree's descriptor
-        # sees slab[:slab_cap], the reply encoder the whole allocation
         scratch = (int(scratch) + 15) & ~15
-        self.slab_all = torch.randint(0, 256, (self.slab_cap + scratch,),
-                                      dtype=U8, device=dev, generator=g)
-        self.slab = self.slab_all[:self.slab_cap]
-        self.scratch = self.slab_all[self.slab_cap:] if scratch else None
-        self.slot_off = torch.arange(cap, dtype=I64, device=dev) * sb
-        self.data_len = torch.zeros(cap, dtype=I32, device=dev)
+        # every spare node may need a fresh path (up to 64 bytes each, in
+        # 16-byte multiples)
+        self._alloc(dev, cap, len(arena) + (cap - nst) * 80 + (1 << 16),
+                    cap * sb, dcap, scratch, hash_factor, watch_cap, acl_cap,
+                    acl_arena_bytes, compact_free,
+                    slab_fill=lambda nb: torch.randint(
+                        0, 256, (nb,), dtype=U8, device=dev, generator=g),
+                    slot_stride=sb)
+        self.path_arena[:len(arena)] = torch.frombuffer(
+            bytearray(arena), dtype=U8).to(dev)
+        self.node_path_off[:nst] = torch.from_numpy(poff).to(dev)
+        self.node_path_len[:nst] = torch.from_numpy(plen).to(dev)
+        # bytes of each node's path storage (the static paths are packed)
+        self.node_path_cap[:nst] = self.node_path_len[:nst]
+        self.node_pw[:nst] = torch.from_numpy(
+            (poff << 24) | plen.astype(np.int64)).to(dev)
+        self.node_parent[:nst] = torch.from_numpy(parents).to(dev)
         if data_dist is not None:
             self.data_len[leaf0:nst] = torch.from_numpy(leaf_dl).to(dev)
         else:
             self.data_len[leaf0:nst] = data_bytes
-        self.slot_cap = torch.full((cap,), dcap, dtype=I32, device=dev)
         nkids = np.zeros(nst, np.int32)
         nkids[0] = ndirs
         nkids[1:leaf0] = np.bincount(np.arange(n_nodes) // fanout,
                                      minlength=ndirs)[:ndirs]
         nk = torch.from_numpy(nkids).to(dev)
+        cnt = [0] * _lib.TC_N
+        cnt[_lib.TC_NODES], cnt[_lib.TC_ZXID] = nst, nst
+        cnt[_lib.TC_PATH_TOP], cnt[_lib.TC_SLAB_TOP] = len(arena), nst * sb
+        self.counters.copy_(torch.tensor(cnt, dtype=I64, device=dev))
+        now = int(time.time() * 1000) if ctime_ms is None else ctime_ms
+        L.tree_fill(self._tensors, 0, nst, nk, now)
+        # shard = (rank, world): this replica indexes only the leaves whose
+        # path hashes to `rank` (zkmi/parallel/sharded.py routes every read
+        # there); the rest stay in the layout, unreachable by lookup
+        self.shard = shard
+        if shard is not None and shard[1] > 1:
+            own = path_owner(enc[leaf0:], shard[1])
+            gone = np.nonzero(own != shard[0])[0] + leaf0
+            self.node_parent[torch.from_numpy(gone).to(dev)] = NODE_FREE
+        L.tree_build(self._tensors, 0, nst)
+        torch.cuda.synchronize(dev)
+
+    def _alloc(self, dev, cap, path_cap, slab_cap, dcap, scratch,
+               hash_factor, watch_cap, acl_cap, acl_arena_bytes,
+               compact_free=False, slab_fill=None, slot_stride=None):
+        """The tensors of an empty tree of ``cap`` node slots, a path arena
+        of ``path_cap`` bytes and a slab of ``slab_cap`` (+ ``scratch``)
+        bytes, with the watch and ACL tables asked for: what the
+        constructor and :meth:`load` share.  Counters, index and node table
+        are all zero / free of content.  ``slab_fill(bytes)`` makes the slab
+        (the constructor's random bytes; default zeros), ``slot_stride``
+        lays the slots out back to back (default: offsets all zero, for the
+        load to set)."""
+        self.device = dev
+        self.cap = cap
+        self.path_cap = path_cap
+        self.path_arena = torch.zeros(self.path_cap, dtype=U8, device=dev)
+        self.node_path_off = torch.zeros(cap, dtype=I64, device=dev)
+        self.node_path_len = torch.zeros(cap, dtype=I32, device=dev)
+        self.node_path_cap = torch.zeros(cap, dtype=I32, device=dev)
+        # path word (offset << 24 | length) the hash lookups verify against
+        self.node_pw = torch.zeros(cap, dtype=I64, device=dev)
+        self.node_parent = torch.full((cap,), -1, dtype=I64, device=dev)
+        self.slot = slot_bytes(dcap)
+        self.slab_cap = slab_cap
+        # hash vals pack node (32 bits) and slot offset / 16 (31 bits)
+        assert cap < (1 << 31) and self.slab_cap < (1 << 35), 'tree too big'
+        # scratch: bytes past the tree's slab for the snapshots of ordered
+        # serving (GpuServer.serve(ordered=True)); the tree's descriptor
+        # sees slab[:slab_cap], the reply encoder the whole allocation
+        self.slab_all = slab_fill(self.slab_cap + scratch) \
+            if slab_fill is not None else \
+            torch.zeros(self.slab_cap + scratch, dtype=U8, device=dev)
+        self.slab = self.slab_all[:self.slab_cap]
+        self.scratch = self.slab_all[self.slab_cap:] if scratch else None
+        self.slot_off = torch.zeros(cap, dtype=I64, device=dev) \
+            if slot_stride is None else \
+            torch.arange(cap, dtype=I64, device=dev) * slot_stride
+        self.data_len = torch.zeros(cap, dtype=I32, device=dev)
+        self.slot_cap = torch.full((cap,), dcap, dtype=I32, device=dev)
         # hash entries per node slot (a power of two above it): 2 keeps a
         # read-mostly tree's table under half full; a write-heavy one
         # (SEQUENTIAL names never reused) fills with tombstones between
@@ -200,10 +238,7 @@ class GpuTree(object):
                    _next_pow2(2 * cap))
         # 64-byte entries, empty = all zero bytes (csrc/kernels/zk_tree.h)
         self.ht = torch.zeros(_lib.HT_WORDS * hcap, dtype=I64, device=dev)
-        cnt = [0] * _lib.TC_N
-        cnt[_lib.TC_NODES], cnt[_lib.TC_ZXID] = nst, nst
-        cnt[_lib.TC_PATH_TOP], cnt[_lib.TC_SLAB_TOP] = len(arena), nst * sb
-        self.counters = torch.tensor(cnt, dtype=I64, device=dev)
+        self.counters = torch.zeros(_lib.TC_N, dtype=I64, device=dev)
         self.free_list = torch.empty(cap, dtype=I64, device=dev)
         # host-endian cversion / numChildren / pzxid shadows + dirty list
         # cversion << 32 | numChildren per node (one atomic per child write)
@@ -218,6 +253,7 @@ class GpuTree(object):
         # every served batch (free_compact)
         self.compact_free = compact_free
         self.free_ws = None
+        self.snap_ws = None
         # the tree / node-store descriptor lists torch.ops.zkmi takes
         # (csrc/torch/zkmi_ops.cpp tree() / node_store() field order)
         self.store = [self.slab_all, self.slot_off, self.data_len,
@@ -242,18 +278,116 @@ class GpuTree(object):
         self.acl = None
         if acl_cap > 0:
             self._init_acl(int(acl_cap), acl_arena_bytes)
-        now = int(time.time() * 1000) if ctime_ms is None else ctime_ms
-        L.tree_fill(self._tensors, 0, nst, nk, now)
-        # shard = (rank, world): this replica indexes only the leaves whose
-        # path hashes to `rank` (zkmi/parallel/sharded.py routes every read
-        # there); the rest stay in the layout, unreachable by lookup
-        self.shard = shard
-        if shard is not None and shard[1] > 1:
-            own = path_owner(enc[leaf0:], shard[1])
-            gone = np.nonzero(own != shard[0])[0] + leaf0
-            self.node_parent[torch.from_numpy(gone).to(dev)] = NODE_FREE
-        L.tree_build(self._tensors, 0, nst)
-        torch.cuda.synchronize(dev)
+
+    @classmethod
+    def load(cls, image, device=None, spare=0.25, data_cap=128,
+             hash_factor=2, watch_cap=0, acl_cap=0, scratch=0,
+             acl_arena_bytes=None, nodes=None, path_bytes=None,
+             slab_bytes=None):
+        """A tree holding the znodes of ``image`` (a device or CPU uint8
+        tensor, or ``bytes``: what :meth:`snapshot` or
+        ``zkmi.utils.treeimage.pack`` made), record ``i`` at node ``i``,
+        with room for ``n * (1 + spare)`` nodes as the constructor has for
+        its static ones, ``max(data_cap, data length)`` bytes of data a
+        node, and whatever tables are asked for.  ``nodes`` /
+        ``path_bytes`` / ``slab_bytes`` set a capacity outright.  The zxid
+        counter continues from the image's; ephemerals keep their owner, so
+        an :meth:`expire` of that session removes them; watches and
+        sessions are not part of an image.  Raises
+        ``treeimage.TreeImageError(code, index)`` for an image the device
+        refuses.  One host read of the header, one of the outcome."""
+        from ..utils import treeimage as TI
+        dev = torch.device(device) if device is not None else \
+            torch.device('cuda', torch.cuda.current_device())
+        if isinstance(image, (bytes, bytearray, memoryview)):
+            image = torch.frombuffer(bytearray(image) or bytearray(1),
+                                     dtype=U8)[:len(image)]
+        if image.dtype != U8 or image.dim() != 1:
+            raise ValueError('load: the image is a 1-d uint8 tensor or bytes')
+        length = image.numel()
+        img = image.to(dev).contiguous()
+        if length == 0:
+            img = torch.zeros(16, dtype=U8, device=dev)
+        # sizing only: the device checks every field it uses itself.  What
+        # the header asks for is bounded by what the image can hold (a
+        # record's data and path lie inside the body), so a header that
+        # lies cannot size the tree past a few times the image: it ends as
+        # NO_ROOM or BAD_HEADER on the device
+        n, body, path16, max_data = 0, 0, 0, 0
+        if length >= TI.HEAD:
+            h = TI._HEAD.unpack(bytes(img[:TI.HEAD].cpu().numpy().tobytes()))
+            room = length - TI.HEAD
+            if 0 <= h[3] <= room // 8 - 1 and \
+                    0 <= h[4] <= room - 8 * (h[3] + 1):
+                n, body = h[3], h[4]
+                path16 = min(max(h[7], 0), body + 16 * n)
+                max_data = min(max(h[8], 0), body)
+        dcap = int(data_cap)
+        cap = int(nodes) if nodes is not None else \
+            int(n * (1 + spare)) + 1024
+        cap = max(cap, 1)
+        # the records' slots: each as large as the largest, but no more in
+        # all than the body's bytes over a slot of data_cap each (the data
+        # lies inside the body, so this holds whatever the header says); the
+        # spare ones what a CREATE allocates at least
+        sb = slot_bytes(max(dcap, max_data))
+        slab = min(n * sb, n * slot_bytes(dcap) + body + 16 * n) + \
+            max(cap - n, 0) * slot_bytes(max(dcap, 128))
+        if slab_bytes is not None:
+            slab = max((int(slab_bytes) + 15) & ~15, 16)
+        if cap >= (1 << 31) or slab >= (1 << 35):
+            # (past what a hash val addresses: no tree holds this image)
+            raise TI.TreeImageError(TI.NO_ROOM, -1)
+        self = cls.__new__(cls)
+        self._alloc(dev, cap,
+                    max(int(path_bytes), 16) if path_bytes is not None else
+                    path16 + max(cap - n, 0) * 80 + (1 << 16),
+                    slab, dcap, (int(scratch) + 15) & ~15, hash_factor,
+                    watch_cap, acl_cap, acl_arena_bytes)
+        self.slot = sb
+        self.n_static = n
+        self.leaf0 = self.n_leaves = None
+        self.data_bytes = max_data
+        self.data_dist = None
+        self.shard = None
+        L = _lib.lib()
+        ws = torch.empty(L.tree_load_workspace(n), dtype=U8, device=dev)
+        status = torch.zeros(2, dtype=I64, device=dev)
+        _lib.tree_load(self._tensors, self.acl, img, length, n, dcap, ws,
+                       status)
+        code, index = status.cpu().tolist()
+        if code != TI.OK:
+            raise TI.TreeImageError(code, index)
+        return self
+
+    def snapshot(self, out=None):
+        """The image of the live znodes (csrc/kernels/zk_snap.h), written on
+        the device between batches: a uint8 device tensor of exactly its
+        size (one host read of the size).  With ``out`` (a uint8 device
+        tensor, 16-byte aligned) nothing is read back: returns ``(out,
+        total, status)``, ``total`` a device int64 [2] (image bytes,
+        records) and ``status`` a device int64 [2] whose first word is 0, or
+        ``treeimage.NO_ROOM`` when the image does not fit ``out`` (nothing
+        is written then).  ``total`` and ``status`` are the tree's own two
+        tensors, which the next ``snapshot`` call of this tree writes again:
+        read or clone them before it.  Capturable with ``out``."""
+        L = _lib.lib()
+        if self.snap_ws is None:
+            self.snap_ws = (
+                torch.empty(L.tree_snap_workspace(self.cap), dtype=U8,
+                            device=self.device),
+                torch.zeros(2, dtype=I64, device=self.device),
+                torch.zeros(2, dtype=I64, device=self.device))
+        ws, total, status = self.snap_ws
+        acl = self.acl or []
+        _lib.tree_snap_size(self._tensors, acl, ws, total)
+        if out is not None:
+            _lib.tree_snap_write(self._tensors, acl, ws, out, out.numel(),
+                                 status)
+            return out, total, status
+        img = torch.empty(int(total[0].item()), dtype=U8, device=self.device)
+        _lib.tree_snap_write(self._tensors, acl, ws, img, img.numel(), status)
+        return img
 
     @property
     def tensors(self):

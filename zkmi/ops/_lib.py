@@ -167,6 +167,52 @@ def tree_acl_get(tree, acl, rx, frame_off, frame_len, count, ncap, ws, out,
                        bool(terminate))
 
 
+# outcome of an image load / a fixed-buffer snapshot (csrc/kernels/zk_snap.h
+# SNAP_*; zkmi/utils/treeimage.py mirrors them)
+(SNAP_OK, SNAP_BAD_HEADER, SNAP_BAD_TABLE, SNAP_BAD_RECORD, SNAP_NO_ROOM,
+ SNAP_DUP_PATH, SNAP_ORPHAN, SNAP_DIGEST) = range(8)
+
+
+def tree_snap_workspace(cap):
+    """Bytes of the workspace :func:`tree_snap_size` / :func:`tree_snap_write`
+    need for a tree of ``cap`` node slots (a uint8 tensor; nothing in it
+    needs zeroing)."""
+    return lib().tree_snap_workspace(int(cap))
+
+
+def tree_load_workspace(n):
+    """Bytes of the workspace :func:`tree_load` needs for an image of ``n``
+    records (a uint8 tensor; nothing in it needs zeroing)."""
+    return lib().tree_load_workspace(int(n))
+
+
+def tree_snap_size(tree, acl, ws, total):
+    """Size the image of the tree's live znodes on ``ws``, on the current
+    stream (csrc/kernels/tree_snap.hip): ``total`` (int64 [2]) = image
+    bytes, records.  ``acl``: the tree's ACL table (``GpuTree.acl``) or an
+    empty list.  No host read."""
+    lib().tree_snap_size(tree, list(acl or []), ws, total)
+
+
+def tree_snap_write(tree, acl, ws, out, out_cap, status):
+    """Write the image :func:`tree_snap_size` just sized on ``ws`` into
+    ``out[:out_cap]`` (16-byte aligned).  ``status`` (int64 [2]):
+    :data:`SNAP_OK`, or :data:`SNAP_NO_ROOM` when the image does not fit —
+    nothing is written then.  No host read."""
+    lib().tree_snap_write(tree, list(acl or []), ws, out, int(out_cap),
+                          status)
+
+
+def tree_load(tree, acl, image, image_len, n, data_cap, ws, status):
+    """Load ``image[:image_len]`` (``n`` records by the host's reading of
+    its header; the device checks it) into the fresh, empty ``tree``.
+    ``status`` (int64 [2]): the ``SNAP_*`` outcome and the record index it
+    was found at (-1: none).  A refused image is a normal outcome; the tree
+    is then unusable.  No host read."""
+    lib().tree_load(tree, list(acl or []), image, int(image_len), int(n),
+                    int(data_cap), ws, status)
+
+
 # engine classes of a mixed batch, in engine order (csrc/kernels/zk_mix.h):
 # the fused serve, the GET_ACL path, the list path
 MIX_A, MIX_C, MIX_L = 0, 1, 2
