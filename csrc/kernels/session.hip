@@ -17,24 +17,13 @@
 // timeOut, sessionId, 16-byte passwd, the readOnly byte real servers append,
 // test/streams.test.js:24), so frame i lands at i * 41 with no scan.
 #include "zk_common.h"
+#include "zk_session.h"   // SS_*, sess_slot
 
 namespace zk {
 
 constexpr int SS_T = 256;
 constexpr int32_t CR_RESP_BYTES = 41;
-enum : int32_t { SS_FREE = 0, SS_ALIVE = 1, SS_CLOSED = 2 };
 // (per-request outcomes: SC_* in zk_common.h)
-
-// The table slot of session id s (-1: not one this table can hold).
-ZK_DEV int64_t sess_slot(const ZkSessionTable& tab, int64_t s,
-                         int64_t server_id) {
-  const int64_t srv = (s >> 56) & 0x7f;
-  const int64_t idx = (s & 0x00ffffffffffffffll) - 1;
-  if (idx < 0) return -1;
-  if (tab.span == 0) return srv == server_id && idx < tab.cap ? idx : -1;
-  if (srv < 1 || idx >= tab.span || srv * tab.span > tab.cap) return -1;
-  return (srv - 1) * tab.span + idx;
-}
 
 ZK_DEV uint64_t mix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;

@@ -293,8 +293,23 @@ ZK_DEV int32_t do_create(const ZkTree& t, Lane& L, const uint8_t* data,
 // instead of the table; the workgroup also writes its rows to the table
 // (rows_off / rows_len, what fs_rows would have written) and clears its
 // share of the scan's flags.
+// MS: a session batch (tree_sess.hip): the frames of several connections in
+// one stream.  A live frame takes its session and watcher slot from its
+// segment's row of the table M instead of the launch's scalars; when the
+// table is unsound (*M.bad != 0) every request is answered SYSTEMERROR, and
+// a request of a segment whose session is not alive SESSION_EXPIRED — both
+// as the ordered passes refuse a request: nothing is looked up, claimed,
+// written, armed or fired.
+struct ServeSegs {
+  const int32_t* f_seg;      // [ncap] frame -> segment
+  const int64_t* sessions;   // [S]
+  const int32_t* wslots;     // [S]
+  const int32_t* seg_state;  // [S] 0 serve, 1 session not alive
+  const int64_t* bad;        // [2] != 0: the table is unsound
+  int64_t S;
+};
 static_assert(TR_T == FR_T, "a workgroup per block of FR_T frames");
-template <bool PARSE, bool RO, bool TILES>
+template <bool PARSE, bool RO, bool TILES, bool MS = false>
 ZK_DEV void tree_serve_body(
     const ZkTree& t, const uint8_t* __restrict__ rx, const ZkReqOut& q,
     const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
@@ -307,7 +322,8 @@ ZK_DEV void tree_serve_body(
     const uint8_t* __restrict__ rank, int32_t pass, int32_t last_pass,
     int64_t snap_base, int64_t snap_cap, int64_t* __restrict__ snap_top,
     int32_t wslot, int64_t* __restrict__ fired, const ZkFrameTiles* T,
-    int64_t* __restrict__ rows_off, int32_t* __restrict__ rows_len) {
+    int64_t* __restrict__ rows_off, int32_t* __restrict__ rows_len,
+    const ServeSegs* M = nullptr) {
   session = sess_of(t, session);
   const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);
   const int64_t i = (int64_t)blk * TR_T + threadIdx.x;
@@ -330,7 +346,18 @@ ZK_DEV void tree_serve_body(
   const int32_t rb = rank != nullptr && in_batch ? (int32_t)rank[i] : 0;
   const int32_t rk = rb & ORD_RANK;
   const bool live = in_batch && (rk == pass || (last_pass && rk > pass));
-  const bool refused = live && rk > pass;
+  int32_t ms_err = ERR_OK;           // MS: the segment's refusal
+  if (MS && live) {
+    const int64_t sg = M->f_seg[i];
+    if (*M->bad != 0 || sg < 0 || sg >= M->S) {
+      ms_err = ERR_SYSTEM;
+    } else {
+      session = sess_of(t, M->sessions[sg]);
+      wslot = M->wslots[sg];
+      if (M->seg_state[sg] == 1) ms_err = ERR_SESSION_EXPIRED;
+    }
+  }
+  const bool refused = live && (rk > pass || (MS && ms_err != ERR_OK));
   ReqFields rq{ST_BAD_DECODE, 0, OP_PING, 0, 0, 0, 0, -1, -1, -1, 0};
   if (live) {
     if (PARSE) {
@@ -352,7 +379,8 @@ ZK_DEV void tree_serve_body(
   const ZkNodeStore& s = t.store;
   Lane L;
   L.op = live ? rq.op : OP_PING;
-  L.err = refused ? ERR_SYSTEM : (live && !ok_req ? ERR_BAD_ARGUMENTS : ERR_OK);
+  L.err = refused ? (MS && ms_err != ERR_OK ? ms_err : ERR_SYSTEM)
+                  : (live && !ok_req ? ERR_BAD_ARGUMENTS : ERR_OK);
   L.node = -1;
   L.slot = -1;
   L.dlen = 0;
@@ -514,7 +542,10 @@ ZK_DEV void tree_serve_body(
         L.err = ERR_UNIMPLEMENTED;
     }
   }
-  if (numbered) cn_add(t, seq_par(t, i), 0, -1);
+  // (MS, the whole batch refused: no number of the ordering pass's bump was
+  // used, so the parent's cversion goes back with the child)
+  if (numbered)
+    cn_add(t, seq_par(t, i), MS && ms_err == ERR_SYSTEM ? -1 : 0, -1);
   // ---- watches: reads with watch=1 arm (this session's slot), successful
   // writes fire (lib/zk-session.js:558-574 is the client side of the
   // trigger table; the server rules are SURVEY Appendix D)
@@ -638,6 +669,23 @@ __global__ __launch_bounds__(TR_T) void tree_serve_tiles_k(
       fired, &T, rows_off, rows_len);
 }
 
+// The serve of a session batch (MS; the plain and the ordered passes' form).
+template <bool PARSE>
+__global__ __launch_bounds__(TR_T) void tree_serve_sess_k(
+    ZkTree t, const uint8_t* __restrict__ rx, ZkReqOut q,
+    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
+    const int64_t* __restrict__ n_dev, int64_t ncap, ZkServeOut o,
+    int64_t now_ms, const uint8_t* __restrict__ rank, int32_t pass,
+    int32_t last_pass, int64_t snap_base, int64_t snap_cap,
+    int64_t* __restrict__ snap_top, int64_t* __restrict__ fired,
+    ServeSegs M) {
+  tree_serve_body<PARSE, false, false, true>(
+      t, rx, q, foff, flen, n_dev, ncap, o.opcode, o.xid, o.err, o.node,
+      o.zxid, o.path_off, o.path_len, o.slot, o.sizes, o.block_sums, 0,
+      now_ms, rank, pass, last_pass, snap_base, snap_cap, snap_top, -1, fired,
+      nullptr, nullptr, nullptr, &M);
+}
+
 // The one launch site of tree_serve_k (zk_tree.h ServeLaunch): its
 // <false, false>, <true, false> and <true, true> instances, and the two of
 // tree_serve_tiles_k.
@@ -647,7 +695,7 @@ int serve_launch(const ServeLaunch& s, hipStream_t st) {
   if ((o.sizes == nullptr) != (o.block_sums == nullptr)) return -1;
   if (s.tiles != nullptr) {
     // after a rows-deferred scan: the frame table receives the rows
-    if (s.q != nullptr || s.rank != nullptr) return -1;
+    if (s.q != nullptr || s.rank != nullptr || s.f_seg != nullptr) return -1;
     const auto kt = s.read_only ? tree_serve_tiles_k<true>
                                 : tree_serve_tiles_k<false>;
     kt<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T, 0, st>>>(
@@ -657,6 +705,21 @@ int serve_launch(const ServeLaunch& s, hipStream_t st) {
     return 0;
   }
   const bool parse = s.q == nullptr;
+  if (s.f_seg != nullptr) {
+    // a session batch: the MS instances (none read-only, none over tiles)
+    if (s.read_only || s.sessions == nullptr || s.wslots == nullptr ||
+        s.seg_state == nullptr || s.bad == nullptr || s.nseg < 1)
+      return -1;
+    const ServeSegs M{s.f_seg, s.sessions, s.wslots, s.seg_state, s.bad,
+                      s.nseg};
+    const auto km = parse ? tree_serve_sess_k<true> : tree_serve_sess_k<false>;
+    km<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T, 0, st>>>(
+        *s.tree, s.rx, parse ? ZkReqOut{} : *s.q, s.foff, s.flen, s.n_dev,
+        s.ncap, o, s.now_ms, s.rank, s.pass, s.last_pass, s.snap_base,
+        s.snap_cap, s.snap_top, s.fired, M);
+    ZK_LAUNCH_CHECK();
+    return 0;
+  }
   const auto k = !parse        ? tree_serve_k<false>
                  : s.read_only ? tree_serve_k<true, true>
                                : tree_serve_k<true>;
@@ -703,6 +766,25 @@ int zk_tree_serve_frames(const ZkTree* t, const uint8_t* rx,
   s.tree = t, s.rx = rx, s.foff = foff, s.flen = flen, s.n_dev = n_dev;
   s.ncap = ncap, s.out = out, s.session = session, s.now_ms = now_ms;
   s.wslot = wslot, s.fired = fired, s.read_only = read_only;
+  return zk::serve_launch(s, st);
+}
+
+// zk_tree_serve_frames for a session batch: session and watcher slot per
+// segment (zk_sess_assign's f_seg / seg_state / bad, the caller's sessions /
+// wslots [nseg]).  No finish, like zk_tree_serve_frames.
+int zk_tree_serve_frames_sessions(
+    const ZkTree* t, const uint8_t* rx, const int64_t* foff,
+    const int32_t* flen, const int64_t* n_dev, int64_t ncap,
+    const ZkServeOut* out, int64_t now_ms, int64_t* fired,
+    const int32_t* f_seg, const int64_t* sessions, const int32_t* wslots,
+    const int32_t* seg_state, const int64_t* bad, int64_t nseg,
+    hipStream_t st) {
+  if (f_seg == nullptr) return (int)hipErrorInvalidValue;
+  zk::ServeLaunch s;
+  s.tree = t, s.rx = rx, s.foff = foff, s.flen = flen, s.n_dev = n_dev;
+  s.ncap = ncap, s.out = out, s.now_ms = now_ms, s.fired = fired;
+  s.f_seg = f_seg, s.sessions = sessions, s.wslots = wslots;
+  s.seg_state = seg_state, s.bad = bad, s.nseg = nseg;
   return zk::serve_launch(s, st);
 }
 

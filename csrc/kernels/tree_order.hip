@@ -285,12 +285,15 @@ int64_t zk_tree_order_workspace(int64_t ncap) {
 // answered SYSTEMERROR and shows in the max rank (zk_tree_order_stats_offset;
 // the caller can read it and use more passes).  The launches do not depend
 // on the ranks: no host read.
-int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
-                          const int64_t* n_dev, int64_t ncap,
-                          const ZkServeOut* out, int64_t session,
-                          int64_t now_ms, uint8_t* ws, int64_t ws_bytes,
-                          int32_t passes, int64_t snap_base, int64_t snap_cap,
-                          int32_t wslot, int64_t* fired, hipStream_t st) {
+// (segs: a session batch's table, ServeLaunch's f_seg .. nseg; null: one
+// session, one watcher slot)
+static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
+                         const int64_t* n_dev, int64_t ncap,
+                         const ZkServeOut* out, int64_t session,
+                         int64_t now_ms, uint8_t* ws, int64_t ws_bytes,
+                         int32_t passes, int64_t snap_base, int64_t snap_cap,
+                         int32_t wslot, int64_t* fired,
+                         const zk::ServeLaunch* segs, hipStream_t st) {
   if (ncap <= 0) return 0;
   if (ncap > zk::ORD_FM) return -1;          // packed group counts
   if (passes < 1 || passes > zk::ORD_RANK) return -1;
@@ -325,6 +328,11 @@ int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
   s.out = out, s.session = session, s.now_ms = now_ms, s.rank = rank;
   s.snap_base = snap_base, s.snap_cap = snap_cap, s.snap_top = &w.ctr[2];
   s.wslot = wslot, s.fired = fired;
+  if (segs != nullptr) {
+    s.f_seg = segs->f_seg, s.sessions = segs->sessions;
+    s.wslots = segs->wslots, s.seg_state = segs->seg_state;
+    s.bad = segs->bad, s.nseg = segs->nseg;
+  }
   for (s.pass = 0; s.pass < passes; ++s.pass) {
     const int32_t last = s.pass == passes - 1;
     s.last_pass = last;
@@ -336,6 +344,35 @@ int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
     if (rc) return rc;
   }
   return 0;
+}
+
+int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
+                          const int64_t* n_dev, int64_t ncap,
+                          const ZkServeOut* out, int64_t session,
+                          int64_t now_ms, uint8_t* ws, int64_t ws_bytes,
+                          int32_t passes, int64_t snap_base, int64_t snap_cap,
+                          int32_t wslot, int64_t* fired, hipStream_t st) {
+  return ordered_serve(t, rx, q, n_dev, ncap, out, session, now_ms, ws,
+                       ws_bytes, passes, snap_base, snap_cap, wslot, fired,
+                       nullptr, st);
+}
+
+// zk_tree_serve_ordered for a session batch (zk_tree_serve_frames_sessions'
+// table): requests on one path are applied in stream order whichever
+// segments they come from.
+int zk_tree_serve_ordered_sessions(
+    const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
+    const int64_t* n_dev, int64_t ncap, const ZkServeOut* out, int64_t now_ms,
+    uint8_t* ws, int64_t ws_bytes, int32_t passes, int64_t snap_base,
+    int64_t snap_cap, int64_t* fired, const int32_t* f_seg,
+    const int64_t* sessions, const int32_t* wslots, const int32_t* seg_state,
+    const int64_t* bad, int64_t nseg, hipStream_t st) {
+  if (f_seg == nullptr) return (int)hipErrorInvalidValue;
+  zk::ServeLaunch m;
+  m.f_seg = f_seg, m.sessions = sessions, m.wslots = wslots;
+  m.seg_state = seg_state, m.bad = bad, m.nseg = nseg;
+  return ordered_serve(t, rx, q, n_dev, ncap, out, 0, now_ms, ws, ws_bytes,
+                       passes, snap_base, snap_cap, -1, fired, &m, st);
 }
 
 // Byte offset in the ordering workspace of {max rank, scratch bytes used}

@@ -447,6 +447,43 @@ int zk_session_install(const ZkSessionTable*, const int64_t*, int64_t,
                        int64_t, hipStream_t);
 int zk_scan_small_i64(const int64_t*, int64_t*, int64_t, int64_t*,
                       hipStream_t);
+// Session batches (tree_sess.hip; the rule: zk_sess.h).  zk_sess_assign:
+// (frames off / len, count, ncap, starts[S + 1], sessions[S], S, the session
+// table or null, its server id) -> f_seg[ncap], first[S + 1], seg_state[S],
+// bad[2].  The serves take (..., fired, f_seg, sessions, wslots, seg_state,
+// bad, S) in place of one session and one watcher slot.  zk_sess_ranges:
+// (first, S, the reply encode's rec_off / count / ncap / total / err) ->
+// rep_off[S + 1], and with slot_first (the grouped notification encode's
+// rec_off / count / ecap / total / err) slot_off[65].  zk_sess_group_events:
+// int64 words of its workspace; (ev_slot / type / poff / plen, ev_total,
+// ecap, workspace) -> the records in slot-major order and slot_first[65].
+int zk_sess_assign(const int64_t*, const int32_t*, const int64_t*, int64_t,
+                   const int64_t*, const int64_t*, int64_t,
+                   const ZkSessionTable*, int64_t, int32_t*, int64_t*,
+                   int32_t*, int64_t*, hipStream_t);
+int zk_tree_serve_frames_sessions(const ZkTree*, const uint8_t*,
+                                  const int64_t*, const int32_t*,
+                                  const int64_t*, int64_t, const ZkServeOut*,
+                                  int64_t, int64_t*, const int32_t*,
+                                  const int64_t*, const int32_t*,
+                                  const int32_t*, const int64_t*, int64_t,
+                                  hipStream_t);
+int zk_tree_serve_ordered_sessions(const ZkTree*, const uint8_t*,
+                                   const ZkReqOut*, const int64_t*, int64_t,
+                                   const ZkServeOut*, int64_t, uint8_t*,
+                                   int64_t, int32_t, int64_t, int64_t,
+                                   int64_t*, const int32_t*, const int64_t*,
+                                   const int32_t*, const int32_t*,
+                                   const int64_t*, int64_t, hipStream_t);
+int zk_sess_ranges(const int64_t*, int64_t, const int64_t*, const int64_t*,
+                   int64_t, const int64_t*, const int32_t*, int64_t*,
+                   const int64_t*, const int64_t*, const int64_t*, int64_t,
+                   const int64_t*, const int32_t*, int64_t*, hipStream_t);
+int64_t zk_sess_group_workspace(int64_t ecap);
+int zk_sess_group_events(const int32_t*, const int32_t*, const int64_t*,
+                         const int32_t*, const int64_t*, int64_t, int64_t*,
+                         int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
+                         hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

@@ -34,7 +34,7 @@ enum : int32_t { ERR_OK = 0, ERR_SYSTEM = -1, ERR_UNIMPLEMENTED = -6,
                  ERR_BAD_ARGUMENTS = -8, ERR_NO_NODE = -101,
                  ERR_BAD_VERSION = -103, ERR_NO_CHILDREN_FOR_EPHEMERALS = -108,
                  ERR_NODE_EXISTS = -110, ERR_NOT_EMPTY = -111,
-                 ERR_INVALID_ACL = -114 };
+                 ERR_SESSION_EXPIRED = -112, ERR_INVALID_ACL = -114 };
 // per-record decode status
 enum : int32_t { ST_OK = 0, ST_BAD_DECODE = 1, ST_NO_XID = 2,
                  ST_BAD_OPCODE = 3 };

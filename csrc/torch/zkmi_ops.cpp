@@ -838,6 +838,206 @@ void tree_serve_ordered(const std::vector<Tensor>& t, const Tensor& rx,
          "tree_serve_ordered");
 }
 
+// -- session batches (csrc/kernels/tree_sess.hip) ---------------------------
+
+// The segment table of a session batch as the serves read it: f_seg [ncap],
+// and sessions / wslots / seg_state [S], bad [2].
+struct SegPtrs {
+  const int32_t* f_seg;
+  const int64_t* sessions;
+  const int32_t* wslots;
+  const int32_t* seg_state;
+  const int64_t* bad;
+  int64_t S;
+};
+
+SegPtrs seg_ptrs(const Tensor& f_seg, const Tensor& sessions,
+                 const Tensor& wslots, const Tensor& seg_state,
+                 const Tensor& bad, int64_t ncap, const Tensor* d) {
+  SegPtrs m;
+  m.S = sessions.numel();
+  TORCH_CHECK(m.S >= 1, "zkmi: a segment table has at least one segment");
+  m.f_seg = P<int32_t>(f_seg, I32, ncap, "f_seg", d);
+  m.sessions = P<int64_t>(sessions, I64, m.S, "sessions", d);
+  m.wslots = P<int32_t>(wslots, I32, m.S, "wslots", d);
+  TORCH_CHECK(wslots.numel() == m.S, "zkmi: wslots has ", wslots.numel(),
+              " entries, sessions ", m.S);
+  m.seg_state = P<int32_t>(seg_state, I32, m.S, "seg_state", d);
+  m.bad = P<int64_t>(bad, I64, 2, "bad", d);
+  return m;
+}
+
+// Frames -> segments, segments -> first frames and states, the table's
+// faults (zk_sess.h).  table: the session table's tensors for the liveness
+// check, or an empty list.
+void sess_assign(const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
+                 int64_t ncap, const Tensor& starts, const Tensor& sessions,
+                 const std::vector<Tensor>& table, int64_t server_id,
+                 int64_t span, const Tensor& f_seg, const Tensor& first,
+                 const Tensor& seg_state, const Tensor& bad) {
+  const Tensor* d = &foff;
+  const int64_t S = sessions.numel();
+  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(ncap >= 0, "zkmi: sess_assign ncap");
+  TORCH_CHECK(starts.numel() == S + 1, "zkmi: starts has ", starts.numel(),
+              " entries, needs ", S + 1);
+  ZkSessionTable tab{};
+  const bool has_tab = !table.empty();
+  if (has_tab) {
+    tab = session_table(table, span);
+    TORCH_CHECK(table[0].device() == d->device(),
+                "zkmi: session table on the batch's device");
+    TORCH_CHECK(server_id >= 0 && server_id < 128, "zkmi: server_id");
+  }
+  hip_ok(zk_sess_assign(
+             P<int64_t>(foff, I64, ncap, "frame_off"),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int64_t>(starts, I64, S + 1, "starts", d),
+             P<int64_t>(sessions, I64, S, "sessions", d), S,
+             has_tab ? &tab : nullptr, server_id,
+             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
+             P<int64_t>(first, I64, S + 1, "first", d),
+             P<int32_t>(seg_state, I32, S, "seg_state", d),
+             P<int64_t>(bad, I64, 2, "bad", d), cur_stream()),
+         "sess_assign");
+}
+
+// tree_serve_frames for a session batch (no read-only form).
+void tree_serve_frames_sessions(
+    const std::vector<Tensor>& t, const Tensor& rx, const Tensor& foff,
+    const Tensor& flen, const Tensor& n_dev, int64_t ncap,
+    const std::vector<Tensor>& r, int64_t now_ms,
+    const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
+    const Tensor& f_seg, const Tensor& sessions, const Tensor& wslots,
+    const Tensor& seg_state, const Tensor& bad) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkServeOut ro = serve_out(r, ncap, d);
+  s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
+  const SegPtrs m = seg_ptrs(f_seg, sessions, wslots, seg_state, bad, ncap, d);
+  hip_ok(zk_tree_serve_frames_sessions(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms,
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.f_seg,
+             m.sessions, m.wslots, m.seg_state, m.bad, m.S, cur_stream()),
+         "tree_serve_frames_sessions");
+}
+
+// tree_serve_ordered for a session batch.
+void tree_serve_ordered_sessions(
+    const std::vector<Tensor>& t, const Tensor& rx,
+    const std::vector<Tensor>& q, const Tensor& n_dev, int64_t ncap,
+    const std::vector<Tensor>& r, int64_t now_ms, const Tensor& ws,
+    int64_t passes, const c10::optional<Tensor>& scratch,
+    const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
+    const Tensor& f_seg, const Tensor& sessions, const Tensor& wslots,
+    const Tensor& seg_state, const Tensor& bad) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
+  ZkReqOut qo = req_out(q, ncap, d);
+  ZkServeOut ro = serve_out(r, ncap, d);
+  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
+  const int64_t need_ws = zk_tree_order_workspace(ncap);
+  uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
+  int64_t snap_base = 0, snap_cap = 0;
+  if (scratch.has_value() && scratch->defined()) {
+    const Tensor& sc = *scratch;
+    P<uint8_t>(sc, U8, 0, "scratch", d);
+    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
+                "zkmi: scratch must be a view of the tree's slab");
+    snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
+                          (const uint8_t*)t[6].data_ptr());
+    TORCH_CHECK(snap_base >= s.slab_cap && snap_base % 16 == 0,
+                "zkmi: scratch must start 16-aligned past the tree's slab");
+    snap_cap = sc.numel();
+  }
+  const SegPtrs m = seg_ptrs(f_seg, sessions, wslots, seg_state, bad, ncap, d);
+  hip_ok(zk_tree_serve_ordered_sessions(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms, w,
+             ws.numel(), (int32_t)passes, snap_base, snap_cap,
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.f_seg,
+             m.sessions, m.wslots, m.seg_state, m.bad, m.S, cur_stream()),
+         "tree_serve_ordered_sessions");
+}
+
+// rep_off [S + 1] from the reply encode's rec_off; with slot_first, slot_off
+// [65] from the grouped notification encode's.
+void sess_ranges(const Tensor& first, const Tensor& rec_off,
+                 const Tensor& n_dev, int64_t ncap, const Tensor& total,
+                 const Tensor& err, const Tensor& rep_off,
+                 const c10::optional<Tensor>& slot_first,
+                 const c10::optional<Tensor>& ev_rec_off,
+                 const c10::optional<Tensor>& ev_count,
+                 const c10::optional<Tensor>& ev_bytes,
+                 const c10::optional<Tensor>& ev_err,
+                 const c10::optional<Tensor>& slot_off) {
+  const Tensor* d = &first;
+  const int64_t S = first.numel() - 1;
+  TORCH_CHECK(S >= 1, "zkmi: first needs S + 1 >= 2 entries");
+  TORCH_CHECK(ncap >= 0, "zkmi: sess_ranges ncap");
+  const int64_t* sf = Popt<int64_t>(slot_first, I64, 65, "slot_first", d);
+  int64_t ecap = 0;
+  const int64_t *ero = nullptr, *ec = nullptr, *eb = nullptr;
+  const int32_t* ee = nullptr;
+  int64_t* so = nullptr;
+  if (sf != nullptr) {
+    TORCH_CHECK(ev_rec_off.has_value() && ev_count.has_value() &&
+                    ev_bytes.has_value() && ev_err.has_value() &&
+                    slot_off.has_value(),
+                "zkmi: sess_ranges: slot_first needs the notification "
+                "encode's tensors");
+    ecap = ev_rec_off->numel();
+    ero = P<int64_t>(*ev_rec_off, I64, 1, "ev_rec_off", d);
+    ec = P<int64_t>(*ev_count, I64, 1, "ev_count", d);
+    eb = P<int64_t>(*ev_bytes, I64, 1, "ev_bytes", d);
+    ee = P<int32_t>(*ev_err, I32, 1, "ev_err", d);
+    so = P<int64_t>(*slot_off, I64, 65, "slot_off", d);
+  }
+  hip_ok(zk_sess_ranges(P<int64_t>(first, I64, S + 1, "first"), S,
+                        P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+                        P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+                        P<int64_t>(total, I64, 1, "total", d),
+                        P<int32_t>(err, I32, 1, "err", d),
+                        P<int64_t>(rep_off, I64, S + 1, "rep_off", d), sf, ero,
+                        ec, ecap, eb, ee, so, cur_stream()),
+         "sess_ranges");
+}
+
+int64_t sess_group_workspace(int64_t ecap) {
+  TORCH_CHECK(ecap >= 1, "zkmi: sess_group_workspace ecap");
+  return zk_sess_group_workspace(ecap);
+}
+
+// watch_events' records -> slot-major order (stable) + slot_first [65].
+void sess_group_events(const Tensor& ev_slot, const Tensor& ev_type,
+                       const Tensor& ev_poff, const Tensor& ev_plen,
+                       const Tensor& ev_total, const Tensor& ws,
+                       const Tensor& g_slot, const Tensor& g_type,
+                       const Tensor& g_poff, const Tensor& g_plen,
+                       const Tensor& slot_first) {
+  const Tensor* d = &ev_slot;
+  const int64_t cap = ev_slot.numel();
+  TORCH_CHECK(cap >= 1, "zkmi: sess_group_events: no room for an event");
+  hip_ok(zk_sess_group_events(
+             P<int32_t>(ev_slot, I32, cap, "ev_slot"),
+             P<int32_t>(ev_type, I32, cap, "ev_type", d),
+             P<int64_t>(ev_poff, I64, cap, "ev_path_off", d),
+             P<int32_t>(ev_plen, I32, cap, "ev_path_len", d),
+             P<int64_t>(ev_total, I64, 2, "ev_total", d), cap,
+             P<int64_t>(ws, I64, zk_sess_group_workspace(cap), "workspace", d),
+             P<int32_t>(g_slot, I32, cap, "g_slot", d),
+             P<int32_t>(g_type, I32, cap, "g_type", d),
+             P<int64_t>(g_poff, I64, cap, "g_path_off", d),
+             P<int32_t>(g_plen, I32, cap, "g_path_len", d),
+             P<int64_t>(slot_first, I64, 65, "slot_first", d), cur_stream()),
+         "sess_group_events");
+}
+
 void watch_events(const Tensor& r_op, const Tensor& r_err, const Tensor& n_dev,
                   int64_t ncap, const Tensor& fired, const Tensor& bsum,
                   const Tensor& ev_slot, const Tensor& ev_type,
@@ -1644,6 +1844,31 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(c!) ws, int passes, Tensor? scratch, int wslot=-1, "
         "Tensor(d!)? fired=None, Tensor? seqno=None) -> ()",
         &tree_serve_ordered);
+  m.def("sess_assign(Tensor frame_off, Tensor frame_len, Tensor count, "
+        "int ncap, Tensor starts, Tensor sessions, Tensor[] table, "
+        "int server_id, int span, Tensor(a!) f_seg, Tensor(b!) first, "
+        "Tensor(c!) seg_state, Tensor(d!) bad) -> ()", &sess_assign);
+  m.def("tree_serve_frames_sessions(Tensor(a!)[] tree, Tensor rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor(b!)[] out, int now_ms, Tensor(c!)? fired, Tensor? seqno, "
+        "Tensor f_seg, Tensor sessions, Tensor wslots, Tensor seg_state, "
+        "Tensor bad) -> ()", &tree_serve_frames_sessions);
+  m.def("tree_serve_ordered_sessions(Tensor(a!)[] tree, Tensor rx, "
+        "Tensor[] requests, Tensor count, int ncap, Tensor(b!)[] out, "
+        "int now_ms, Tensor(c!) ws, int passes, Tensor? scratch, "
+        "Tensor(d!)? fired, Tensor? seqno, Tensor f_seg, Tensor sessions, "
+        "Tensor wslots, Tensor seg_state, Tensor bad) -> ()",
+        &tree_serve_ordered_sessions);
+  m.def("sess_ranges(Tensor first, Tensor rec_off, Tensor count, int ncap, "
+        "Tensor total, Tensor err, Tensor(a!) rep_off, "
+        "Tensor? slot_first=None, Tensor? ev_rec_off=None, "
+        "Tensor? ev_count=None, Tensor? ev_bytes=None, Tensor? ev_err=None, "
+        "Tensor(b!)? slot_off=None) -> ()", &sess_ranges);
+  m.def("sess_group_workspace(int ecap) -> int", &sess_group_workspace);
+  m.def("sess_group_events(Tensor ev_slot, Tensor ev_type, Tensor ev_poff, "
+        "Tensor ev_plen, Tensor ev_total, Tensor(a!) ws, Tensor(b!) g_slot, "
+        "Tensor(c!) g_type, Tensor(d!) g_poff, Tensor(e!) g_plen, "
+        "Tensor(f!) slot_first) -> ()", &sess_group_events);
   m.def("tree_seq_workspace(int n) -> int", &tree_seq_workspace);
   m.def("tree_seq_zeroed(int n) -> int", &tree_seq_zeroed);
   m.def("tree_seq_debug(Tensor buf) -> ()", &tree_seq_debug);

@@ -620,6 +620,37 @@ class _SubFrames(object):
         self.off, self.length, self.count = off, length, count
 
 
+class SessionSegments(object):
+    """The segment table of a session batch (:meth:`GpuServer.
+    serve_sessions`; the rule: csrc/kernels/zk_sess.h): the batch is the
+    whole frames of ``S`` connections, concatenated; connection s's bytes are
+    ``rx[starts[s]:starts[s + 1]]``, its EPHEMERAL creates belong to
+    ``sessions[s]`` and its reads arm watcher slot ``wslots[s]`` (-1: none).
+    Device tensors: ``starts`` int64 [S + 1] (non-decreasing, ``starts[0]``
+    0), ``sessions`` int64 [S], ``wslots`` int32 [S]."""
+
+    def __init__(self, starts, sessions, wslots):
+        S = int(sessions.numel())
+        if S < 1 or int(starts.numel()) != S + 1 or int(wslots.numel()) != S:
+            raise ValueError('SessionSegments: starts [S + 1], sessions [S] '
+                             'and wslots [S] with S >= 1')
+        self.starts, self.sessions, self.wslots = starts, sessions, wslots
+        self.S = S
+
+
+class _SegState(object):
+    """What :meth:`GpuServer.serve_sessions` leaves on the device about the
+    last session batch's segments."""
+
+    def __init__(self, cap_frames, S, dev):
+        self.S = S
+        self.f_seg = torch.zeros(cap_frames, dtype=I32, device=dev)
+        self.first = torch.zeros(S + 1, dtype=I64, device=dev)
+        self.rep_off = torch.zeros(S + 1, dtype=I64, device=dev)
+        self.state = torch.zeros(S, dtype=I32, device=dev)
+        self.bad = torch.zeros(2, dtype=I64, device=dev)
+
+
 class GpuServer(object):
     """Server half of the pipeline: frame-scan + decode requests, apply them
     to a :class:`GpuTree`, encode replies."""
@@ -675,6 +706,9 @@ class GpuServer(object):
         self.ows = None                   # ordered-serve workspace (lazy)
         self.total_err = B._total_err(dev)  # the reply encode's scalars
         self.notif = None
+        self.seg = None                   # the last session batch's segments
+        self.notif_slots = None           # (slot_first, slot_off) of its
+        self._grouped = None              # notifications (buffers: lazy)
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -940,6 +974,168 @@ class GpuServer(object):
                 if wslot < 0:
                     raise ValueError('resume needs the watcher slot')
                 self._resume(rx, ft, wslot)
+
+    # -- session batches ------------------------------------------------------
+
+    def _notify_grouped(self):
+        """:meth:`_notify` for a session batch: the events of the last serve
+        grouped by watcher slot (csrc/kernels/tree_sess.hip; request order
+        inside a slot) before K13 encodes them, so every watcher's
+        notifications are one slice of the stream.  ``self.notif`` as
+        :meth:`_notify` leaves it, slot-major; the slices come from
+        ``self.notif_slots`` once :func:`_lib.sess_ranges` ran."""
+        L = _lib.lib()
+        dev = self.tree.device
+        if self._grouped is None:
+            ecap = self.ecap
+            g = {'slot': torch.zeros(ecap, dtype=I32, device=dev),
+                 'type': torch.zeros(ecap, dtype=I32, device=dev),
+                 'poff': torch.zeros(ecap, dtype=I64, device=dev),
+                 'plen': torch.zeros(ecap, dtype=I32, device=dev),
+                 'ws': torch.empty(_lib.sess_group_workspace(ecap),
+                                   dtype=I64, device=dev),
+                 'first': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                      device=dev),
+                 'off': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                    device=dev),
+                 'total_err': B._total_err(dev)}
+            g['resp'] = self._notif_batch(g['poff'], g['plen'],
+                                          self.tree.path_arena, g['type'],
+                                          self.ev_total[0:1], ecap, dev)
+            g['rec_off'] = torch.zeros(ecap, dtype=I64, device=dev)
+            self._grouped = g
+        g = self._grouped
+        r = self.resp
+        L.watch_events(r.opcode, r.err, r.count, self.cap_frames, self.fired,
+                       self.wbsum, self.ev_slot, self.ev_type, self.ev_poff,
+                       self.ev_plen, self.ev_total)
+        _lib.sess_group_events(self.ev_slot, self.ev_type, self.ev_poff,
+                               self.ev_plen, self.ev_total, g['ws'],
+                               g['slot'], g['type'], g['poff'], g['plen'],
+                               g['first'])
+        out, rec_off, total, nerr = B.encode_responses(
+            g['resp'], self.tree.store, self.notif_buf.numel(),
+            out=self.notif_buf, total_err=g['total_err'],
+            rec_off=g['rec_off'])
+        self.notif_rec_off = rec_off
+        self.notif_err = nerr
+        self.notif = (out, total, g['slot'], self.ev_total[0:1])
+        self.notif_slots = (g['first'], g['off'])
+
+    def serve_sessions(self, rx, n, segs, ordered=False, passes=4,
+                       terminate=False, table=None):
+        """Serve ``rx[:n]``, the concatenated whole frames of the
+        ``segs.S`` connections of :class:`SessionSegments` ``segs``, as ONE
+        batch: one K1 scan and one serve (``passes`` of them when
+        ``ordered``), each frame for its own segment's session and watcher
+        slot (csrc/kernels/tree_sess.hip, the serve's MS instances).  ``n``
+        is a host length or a device total; nothing is read back and the
+        call is capturable where :meth:`serve` is.  Returns ``(out, total,
+        err, frame table)`` like :meth:`serve`, and leaves
+
+        ``self.seg``          ``.f_seg`` (segment per frame), ``.first``
+                              (first frame per segment, [S + 1]),
+                              ``.rep_off`` ([S + 1]: connection s's replies
+                              are ``out[rep_off[s]:rep_off[s + 1]]``),
+                              ``.state`` ([S]: 1 = session not alive) and
+                              ``.bad`` ([2]);
+        ``self.notif``        as :meth:`serve` does, but slot-major;
+        ``self.notif_slots``  ``(slot_first, slot_off)``, both [65]: watcher
+                              w's notifications are ``notif_buf[slot_off[w]:
+                              slot_off[w + 1]]``, in request order.
+
+        A frame that crosses a segment boundary, a ``starts`` that does not
+        begin at 0 or descends: every request of the batch is answered
+        SYSTEMERROR and nothing is touched (:meth:`session_stats`).
+        ``table``: a :class:`GpuSessionTable`; a segment whose session (other
+        than 0) it does not hold alive has its requests answered
+        SESSION_EXPIRED, without effect.  (A SEQUENTIAL create refused this
+        way leaves a gap in its parent's cversion, as any failed numbered
+        create does.)
+
+        Single-session still: the list ops, GET_ACL and mixed batches
+        (:meth:`serve_list`, :meth:`serve_acl`, :meth:`serve_mixed`) and the
+        SET_WATCHES catch-up — a SET_WATCHES frame here gets its header-only
+        reply and no catch-up.  How a connection's notification slice is
+        interleaved with its reply slice on the socket is the front end's
+        business."""
+        L = _lib.lib()
+        if self.fused_rows or self.read_only:
+            raise ValueError('serve_sessions: no session form of the '
+                             'read-only or the fused-rows serve')
+        if not isinstance(segs, SessionSegments):
+            raise TypeError('serve_sessions: segs is a SessionSegments')
+        tree = self.tree
+        if self.seg is None or self.seg.S != segs.S:
+            self.seg = _SegState(self.cap_frames, segs.S, tree.device)
+        sg = self.seg
+        ft = self.scanner.scan(rx, n)
+        rt = B.decode_requests(rx, ft, out=self.rt) if ordered else None
+        _lib.sess_assign(
+            ft.off, ft.length, ft.count, self.cap_frames, segs.starts,
+            segs.sessions, sg.f_seg, sg.first, sg.state, sg.bad,
+            table=None if table is None else table._tensors,
+            server_id=0 if table is None else table.server_id,
+            span=0 if table is None else table.span)
+        r = self.resp
+        r.count = ft.count
+        out = [r.opcode, r.xid, r.err, r.node, r.zxid, r.path_off,
+               r.path_len, r.slot, self.presized[0], self.presized[1]]
+        now = int(time.time() * 1000)
+        seqno = self._seq_order(rx, ft) if self.seq_order else None
+        fired = self.fired if tree.watch is not None else None
+        if ordered:
+            if self.ows is None:
+                self.ows = torch.empty(
+                    L.tree_order_workspace(self.cap_frames), dtype=U8,
+                    device=tree.device)
+            _lib.tree_serve_ordered_sessions(
+                tree.tensors, rx, rt.tensors(), ft.count, self.cap_frames,
+                out, now, self.ows, passes, tree.scratch, fired, seqno,
+                sg.f_seg, segs.sessions, segs.wslots, sg.state, sg.bad)
+        else:
+            _lib.tree_serve_frames_sessions(
+                tree.tensors, rx, ft.off, ft.length, ft.count,
+                self.cap_frames, out, now, fired, seqno, sg.f_seg,
+                segs.sessions, segs.wslots, sg.state, sg.bad)
+            L.tree_finish_scan(tree.tensors, ft.count, 0, True,
+                               self.cap_frames, self.presized[1],
+                               self.total_err[0])
+        if tree.acl is not None:
+            _lib.tree_acl_record(tree.acl, rx, ft.off, ft.length, ft.count,
+                                 self.cap_frames, r.opcode, r.err, r.node,
+                                 self._acl_workspace())
+        out, rec_off, total, err = B.encode_responses(
+            r, tree.store, self.out.numel(), out=self.out,
+            presized=self.presized, terminate=terminate,
+            total_err=self.total_err, prescanned=not ordered)
+        if tree.compact_free:
+            tree.free_compact()
+        self.last_rec_off = rec_off
+        self.result = (out, total, err, ft)
+        if tree.watch is not None:
+            self._notify_grouped()
+            g = self._grouped
+            _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
+                             total, err, sg.rep_off, g['first'],
+                             g['rec_off'], self.ev_total[0:1],
+                             g['total_err'][0], g['total_err'][1], g['off'])
+        else:
+            _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
+                             total, err, sg.rep_off)
+        return self.result
+
+    def session_stats(self):
+        """Of the last :meth:`serve_sessions` (one host read): ``bad`` (torn
+        frames + faults of the segment table; not 0: the batch was refused),
+        ``first_bad_segment`` (-1: none) and ``expired_segments`` (segments
+        whose session the table did not hold alive)."""
+        if self.seg is None:
+            raise ValueError('session_stats: no session batch was served')
+        sg = self.seg
+        v = torch.cat([sg.bad, (sg.state == 1).sum().view(1)]).cpu().tolist()
+        return {'bad': v[0], 'first_bad_segment': v[1],
+                'expired_segments': v[2]}
 
     def serve_list(self, rx, n, wslot=-1, terminate=False, max_frame=None,
                    out=None):

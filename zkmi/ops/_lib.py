@@ -264,5 +264,77 @@ def tree_mix_merge(cls, sub, count, counts, ncap, streams, rec_offs, totals,
                          ws)
 
 
+# session batches (csrc/kernels/tree_sess.hip; the rule: zk_sess.h)
+SEG_SERVE, SEG_EXPIRED = 0, 1       # seg_state values
+SESS_SLOTS = 64                     # watcher slots of a server
+
+
+def sess_assign(frame_off, frame_len, count, ncap, starts, sessions, f_seg,
+                first, seg_state, bad, table=None, server_id=0, span=0):
+    """A session batch's frames -> segments, on the current stream:
+    ``f_seg`` (int32 [ncap], written for the batch's frames), ``first``
+    (int64 [S + 1]: each segment's first frame), ``seg_state`` (int32 [S]:
+    :data:`SEG_SERVE`, or :data:`SEG_EXPIRED` when ``table`` — a session
+    table's tensors — does not hold the segment's session alive) and ``bad``
+    (int64 [2]: torn frames + faults of the table, the first bad segment or
+    -1).  Two launches, no host read."""
+    lib().sess_assign(frame_off, frame_len, count, int(ncap), starts,
+                      sessions, list(table or []), int(server_id), int(span),
+                      f_seg, first, seg_state, bad)
+
+
+def tree_serve_frames_sessions(tree, rx, frame_off, frame_len, count, ncap,
+                               out, now_ms, fired, seqno, f_seg, sessions,
+                               wslots, seg_state, bad):
+    """``tree_serve_frames`` for a session batch: every frame is served for
+    its segment's session and watcher slot (:func:`sess_assign`'s outputs);
+    a batch with ``bad[0] != 0`` is refused SYSTEMERROR, a segment with state
+    :data:`SEG_EXPIRED` SESSION_EXPIRED.  ``tree_finish_scan`` follows."""
+    lib().tree_serve_frames_sessions(tree, rx, frame_off, frame_len, count,
+                                     int(ncap), out, int(now_ms), fired,
+                                     seqno, f_seg, sessions, wslots,
+                                     seg_state, bad)
+
+
+def tree_serve_ordered_sessions(tree, rx, requests, count, ncap, out, now_ms,
+                                ws, passes, scratch, fired, seqno, f_seg,
+                                sessions, wslots, seg_state, bad):
+    """``tree_serve_ordered`` for a session batch: requests on one path are
+    applied in stream order whichever segments they come from."""
+    lib().tree_serve_ordered_sessions(tree, rx, requests, count, int(ncap),
+                                      out, int(now_ms), ws, int(passes),
+                                      scratch, fired, seqno, f_seg, sessions,
+                                      wslots, seg_state, bad)
+
+
+def sess_ranges(first, rec_off, count, ncap, total, err, rep_off,
+                slot_first=None, ev_rec_off=None, ev_count=None,
+                ev_bytes=None, ev_err=None, slot_off=None):
+    """After the reply encode: ``rep_off`` (int64 [S + 1]) — connection s's
+    replies are ``out[rep_off[s]:rep_off[s + 1]]``.  With ``slot_first``
+    (after the grouped notification encode): ``slot_off`` (int64 [65])
+    likewise per watcher slot.  One launch."""
+    lib().sess_ranges(first, rec_off, count, int(ncap), total, err, rep_off,
+                      slot_first, ev_rec_off, ev_count, ev_bytes, ev_err,
+                      slot_off)
+
+
+def sess_group_workspace(ecap):
+    """int64 words of the workspace :func:`sess_group_events` needs for
+    ``ecap`` events (nothing in it needs zeroing)."""
+    return lib().sess_group_workspace(int(ecap))
+
+
+def sess_group_events(ev_slot, ev_type, ev_poff, ev_plen, ev_total, ws,
+                      g_slot, g_type, g_poff, g_plen, slot_first):
+    """The ``ev_total[0]`` events ``watch_events`` wrote, grouped by watcher
+    slot (stable: request order inside a slot) -> ``g_*``; ``slot_first``
+    (int64 [65]): slot w's records are ``[slot_first[w], slot_first[w +
+    1])``.  A histogram and a scatter around the device-wide scan, no host
+    read."""
+    lib().sess_group_events(ev_slot, ev_type, ev_poff, ev_plen, ev_total, ws,
+                            g_slot, g_type, g_poff, g_plen, slot_first)
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
