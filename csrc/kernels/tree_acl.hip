@@ -2,6 +2,7 @@
 // zk_abi.h), the pass that records a batch's CREATE ACLs and the GET_ACL
 // serve (the tree: zk_tree.h).
 #include "zk_acl.h"
+#include "zk_sess.h"
 
 namespace zk {
 
@@ -229,6 +230,11 @@ __global__ __launch_bounds__(TR_T) void acl_bind_k(
 //     coalesces as well but costs the LDS image, a barrier and the swizzle
 //     for records that are plain copies; the part-wave needs none of them,
 //     and a long vector (up to 16 MiB) simply takes more trips.
+// MS (acl_size_sess_k): the GET_ACL frames of a session batch of any op mix
+// (GpuServer.serve_sessions_mixed).  A frame its segment's row of the table M
+// refuses (zk_sess.h sess_refusal) is sized header-only with the xid alone
+// read: nothing is parsed or looked up.  Refusal is per lane and *M.bad
+// grid-uniform; acl_total_k and acl_write_k see an error request.
 __global__ __launch_bounds__(TR_T) void acl_size_k(
     ZkTree t, ZkAclTable a, const uint8_t* __restrict__ rx,
     const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
@@ -254,6 +260,51 @@ __global__ __launch_bounds__(TR_T) void acl_size_k(
         if (!acl_word_ok(a, word) || nslot < 0 ||
             nslot + STAT_BYTES > t.slab_cap)
           err = ERR_SYSTEM;             // a lost binding
+      }
+    }
+    sz = 4 + 16 + (err == ERR_OK ? (int64_t)acl_len(word) + STAT_BYTES : 0);
+  }
+  w.xid[i] = xid;
+  w.err[i] = err;
+  w.word[i] = word;
+  w.nslot[i] = nslot;
+  w.sizes[i] = sz;
+}
+
+// The MS instance.  (A kernel of its own text: acl_size_k as an instance of a
+// shared body, however its parameters were passed, came out of the compiler
+// 16 to 32 bytes of code away from what it was; tools/kernel_resources.py
+// --diff.)
+__global__ __launch_bounds__(TR_T) void acl_size_sess_k(
+    ZkTree t, ZkAclTable a, const uint8_t* __restrict__ rx,
+    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
+    const int64_t* __restrict__ n_dev, int64_t ncap, AclWs w, SegTable M) {
+  const int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x;
+  if (i >= ncap) return;
+  int32_t err = ERR_OK, xid = 0;
+  int64_t word = 0, nslot = -1, sz = 0;
+  if (i < *n_dev) {
+    err = sess_refusal(M.bad, M.seg_state, M.S, M.f_seg[i]);
+    if (err != ERR_OK) {
+      xid = sess_xid(rx, foff[i], flen[i]);
+    } else {
+      const ReqFields rq = parse_request(rx, foff[i], flen[i]);
+      xid = rq.xid;
+      if (rq.status != ST_OK) {
+        err = ERR_BAD_ARGUMENTS;
+      } else if (rq.op != OP_GET_ACL) {
+        err = ERR_UNIMPLEMENTED;
+      } else {
+        const Found f = tree_lookup(t, rx + rq.poff, rq.pl);
+        if (f.node < 0 || f.node >= a.cap || f.node >= t.store.cap) {
+          err = ERR_NO_NODE;
+        } else {
+          word = a.node_acl[f.node];
+          nslot = f.slot;
+          if (!acl_word_ok(a, word) || nslot < 0 ||
+              nslot + STAT_BYTES > t.slab_cap)
+            err = ERR_SYSTEM;             // a lost binding
+        }
       }
     }
     sz = 4 + 16 + (err == ERR_OK ? (int64_t)acl_len(word) + STAT_BYTES : 0);
@@ -408,12 +459,13 @@ int zk_tree_acl_record(const ZkAclTable* a, const uint8_t* rx,
 // ncap) from the tree and its ACL table: the framed replies in request order
 // -> out[0, *total), their starts -> rec_off[ncap].  *err = 2 and *total = 0
 // when the stream does not fit out_cap.  See acl_size_k above.
-int zk_tree_acl_get(const ZkTree* t, const ZkAclTable* a, const uint8_t* rx,
-                    const int64_t* foff, const int32_t* flen,
-                    const int64_t* n_dev, int64_t ncap, uint8_t* ws,
-                    int64_t ws_bytes, uint8_t* out, int64_t out_cap,
-                    int64_t* rec_off, int64_t* total, int32_t* err,
-                    int32_t terminate, hipStream_t st) {
+static int acl_get_launch(const ZkTree* t, const ZkAclTable* a,
+                          const uint8_t* rx, const int64_t* foff,
+                          const int32_t* flen, const int64_t* n_dev,
+                          int64_t ncap, const zk::SegTable* M, uint8_t* ws,
+                          int64_t ws_bytes, uint8_t* out, int64_t out_cap,
+                          int64_t* rec_off, int64_t* total, int32_t* err,
+                          int32_t terminate, hipStream_t st) {
   if (out_cap < 0) return -1;
   if (ncap <= 0) {
     if (hipMemsetAsync(total, 0, sizeof(int64_t), st) != hipSuccess) return -4;
@@ -430,8 +482,12 @@ int zk_tree_acl_get(const ZkTree* t, const ZkAclTable* a, const uint8_t* rx,
   zk::AclWs w;
   acl_layout(ncap, ws, &w);
   const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
-  zk::acl_size_k<<<nb, zk::TR_T, 0, st>>>(*t, *a, rx, foff, flen, n_dev, ncap,
-                                          w);
+  if (M != nullptr)
+    zk::acl_size_sess_k<<<nb, zk::TR_T, 0, st>>>(*t, *a, rx, foff, flen, n_dev,
+                                                 ncap, w, *M);
+  else
+    zk::acl_size_k<<<nb, zk::TR_T, 0, st>>>(*t, *a, rx, foff, flen, n_dev,
+                                            ncap, w);
   ZK_LAUNCH_CHECK();
   const int rc = zk_scan_excl_i64(w.sizes, rec_off, ncap, total, w.scan, st);
   if (rc) return rc;
@@ -443,6 +499,37 @@ int zk_tree_acl_get(const ZkTree* t, const ZkAclTable* a, const uint8_t* rx,
                                             out);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+int zk_tree_acl_get(const ZkTree* t, const ZkAclTable* a, const uint8_t* rx,
+                    const int64_t* foff, const int32_t* flen,
+                    const int64_t* n_dev, int64_t ncap, uint8_t* ws,
+                    int64_t ws_bytes, uint8_t* out, int64_t out_cap,
+                    int64_t* rec_off, int64_t* total, int32_t* err,
+                    int32_t terminate, hipStream_t st) {
+  return acl_get_launch(t, a, rx, foff, flen, n_dev, ncap, nullptr, ws,
+                        ws_bytes, out, out_cap, rec_off, total, err,
+                        terminate, st);
+}
+
+// zk_tree_acl_get for the GET_ACL frames of a session batch of any op mix:
+// frame i belongs to segment f_seg[i] (zk_sess_split_segments' table of the
+// GET_ACL class) and is served, or refused as zk_sess.h sess_refusal says
+// (zk_sess_assign's seg_state / bad, nseg segments), header only.
+int zk_tree_acl_get_sessions(const ZkTree* t, const ZkAclTable* a,
+                             const uint8_t* rx, const int64_t* foff,
+                             const int32_t* flen, const int64_t* n_dev,
+                             int64_t ncap, const int32_t* f_seg,
+                             const int32_t* seg_state, const int64_t* bad,
+                             int64_t nseg, uint8_t* ws, int64_t ws_bytes,
+                             uint8_t* out, int64_t out_cap, int64_t* rec_off,
+                             int64_t* total, int32_t* err, int32_t terminate,
+                             hipStream_t st) {
+  if (f_seg == nullptr || seg_state == nullptr || bad == nullptr || nseg < 1)
+    return -1;
+  const zk::SegTable M{f_seg, nullptr, seg_state, bad, nseg};
+  return acl_get_launch(t, a, rx, foff, flen, n_dev, ncap, &M, ws, ws_bytes,
+                        out, out_cap, rec_off, total, err, terminate, st);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // The GPU tree's list path, GET_CHILDREN / GET_CHILDREN2 (the tree: zk_tree.h).
 #include "zk_tree.h"
+#include "zk_sess.h"
 
 namespace zk {
 
@@ -29,6 +30,12 @@ namespace zk {
 //  6. list_copy_k, a wave per request: the other requests of a parent copy
 //     the writer's string region; want[] goes back to the sentinel.
 // No host read between the launches.
+// MS (list_mark_sess_k): the list frames of a session batch of any op mix
+// (GpuServer.serve_sessions_mixed).  A frame takes its watcher slot from its
+// segment's row of the table M; a refused one (zk_sess.h sess_refusal) is
+// answered header-only with the xid alone read: nothing is parsed, looked
+// up, claimed in want[] or armed, and the later kernels see an error request
+// (par -1), as a NO_NODE is.  Refusal is per lane and *M.bad grid-uniform.
 constexpr int32_t LS_NONE = 0x7fffffff;        // want[] / writer idle
 constexpr int LS_BYTES = 40;                   // acc: count << 40 | bytes
 constexpr uint64_t LS_BMASK = (1ull << LS_BYTES) - 1;
@@ -47,11 +54,14 @@ struct ListWs {
   int64_t* scan;                // zk_scan_workspace(ncap)
 };
 
-__global__ __launch_bounds__(TR_T) void list_mark_k(
-    ZkTree t, const uint8_t* __restrict__ rx,
-    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
-    const int64_t* __restrict__ n_dev, int64_t ncap, int32_t wslot,
-    int32_t* __restrict__ want, ListWs w) {
+// (The kernels' parameters carry __restrict__; repeated on the inlined body
+// it moved the plain instance's code, tools/kernel_resources.py --diff.)
+template <bool MS>
+ZK_DEV void list_mark_body(
+    const ZkTree& t, const uint8_t* rx,
+    const int64_t* foff, const int32_t* flen,
+    const int64_t* n_dev, int64_t ncap, int32_t wslot,
+    int32_t* want, const ListWs& w, const SegTable& M) {
   const int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x;
   if (i >= ncap) return;
   w.acc[i] = 0;
@@ -60,22 +70,33 @@ __global__ __launch_bounds__(TR_T) void list_mark_k(
   w.lead[i] = LS_NONE;
   int32_t par = -1, err = ERR_OK, xid = 0, op = OP_PING;
   if (i < *n_dev) {
-    const ReqFields rq = parse_request(rx, foff[i], flen[i]);
-    xid = rq.xid;
-    op = rq.op;
-    if (rq.status != ST_OK) {
-      err = ERR_BAD_ARGUMENTS;
-    } else if (op != OP_GET_CHILDREN && op != OP_GET_CHILDREN2) {
-      err = ERR_UNIMPLEMENTED;
+    int32_t ms_err = ERR_OK;           // MS: the segment's refusal
+    if (MS) {
+      const int64_t sg = M.f_seg[i];
+      ms_err = sess_refusal(M.bad, M.seg_state, M.S, sg);
+      if (ms_err == ERR_OK) wslot = M.wslots[sg];
+    }
+    if (MS && ms_err != ERR_OK) {
+      xid = sess_xid(rx, foff[i], flen[i]);
+      err = ms_err;
     } else {
-      const uint8_t* p = rx + rq.poff;
-      const int64_t node = tree_find(t, p, rq.pl);
-      if (node < 0 || node >= t.store.cap) {
-        err = ERR_NO_NODE;            // (no watch on a missing node)
+      const ReqFields rq = parse_request(rx, foff[i], flen[i]);
+      xid = rq.xid;
+      op = rq.op;
+      if (rq.status != ST_OK) {
+        err = ERR_BAD_ARGUMENTS;
+      } else if (op != OP_GET_CHILDREN && op != OP_GET_CHILDREN2) {
+        err = ERR_UNIMPLEMENTED;
       } else {
-        par = (int32_t)node;
-        atomicMin(&want[node], (int32_t)i);
-        if (rq.arg == 1) wt_arm(t, p, rq.pl, WK_CHILD, wslot);
+        const uint8_t* p = rx + rq.poff;
+        const int64_t node = tree_find(t, p, rq.pl);
+        if (node < 0 || node >= t.store.cap) {
+          err = ERR_NO_NODE;            // (no watch on a missing node)
+        } else {
+          par = (int32_t)node;
+          atomicMin(&want[node], (int32_t)i);
+          if (rq.arg == 1) wt_arm(t, p, rq.pl, WK_CHILD, wslot);
+        }
       }
     }
   }
@@ -83,6 +104,23 @@ __global__ __launch_bounds__(TR_T) void list_mark_k(
   w.err[i] = err;
   w.xid[i] = xid;
   w.op[i] = op;
+}
+
+__global__ __launch_bounds__(TR_T) void list_mark_k(
+    ZkTree t, const uint8_t* __restrict__ rx,
+    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
+    const int64_t* __restrict__ n_dev, int64_t ncap, int32_t wslot,
+    int32_t* __restrict__ want, ListWs w) {
+  list_mark_body<false>(t, rx, foff, flen, n_dev, ncap, wslot, want, w,
+                        SegTable{});
+}
+
+__global__ __launch_bounds__(TR_T) void list_mark_sess_k(
+    ZkTree t, const uint8_t* __restrict__ rx,
+    const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
+    const int64_t* __restrict__ n_dev, int64_t ncap,
+    int32_t* __restrict__ want, ListWs w, SegTable M) {
+  list_mark_body<true>(t, rx, foff, flen, n_dev, ncap, -1, want, w, M);
 }
 
 // The sweep over the node table.  FILL = false: count; true: write.  Every
@@ -292,12 +330,14 @@ int64_t zk_tree_list_workspace(int64_t ncap) {
 // leave it so).  A reply frame longer than max_frame bytes (length word
 // included) is answered SYSTEMERROR instead.  *err = 2 and *total = 0 when
 // the stream does not fit out_cap.  See list_* above.
-int zk_tree_list(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
-                 const int32_t* flen, const int64_t* n_dev, int64_t ncap,
-                 int32_t wslot, int64_t max_frame, int32_t* want, uint8_t* ws,
-                 int64_t ws_bytes, uint8_t* out, int64_t out_cap,
-                 int64_t* rec_off, int64_t* total, int32_t* err,
-                 int32_t terminate, hipStream_t st) {
+static int list_launch(const ZkTree* t, const uint8_t* rx,
+                       const int64_t* foff, const int32_t* flen,
+                       const int64_t* n_dev, int64_t ncap, int32_t wslot,
+                       const zk::SegTable* M, int64_t max_frame,
+                       int32_t* want, uint8_t* ws, int64_t ws_bytes,
+                       uint8_t* out, int64_t out_cap, int64_t* rec_off,
+                       int64_t* total, int32_t* err, int32_t terminate,
+                       hipStream_t st) {
   if (out_cap < 0 || max_frame < 0) return -1;
   if (ncap <= 0) {
     if (hipMemsetAsync(total, 0, sizeof(int64_t), st) != hipSuccess) return -4;
@@ -315,8 +355,12 @@ int zk_tree_list(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
   list_layout(ncap, ws, &w);
   const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
   const unsigned nbv = (unsigned)((t->store.cap + zk::TR_T - 1) / zk::TR_T);
-  zk::list_mark_k<<<nb, zk::TR_T, 0, st>>>(*t, rx, foff, flen, n_dev, ncap,
-                                           wslot, want, w);
+  if (M != nullptr)
+    zk::list_mark_sess_k<<<nb, zk::TR_T, 0, st>>>(*t, rx, foff, flen, n_dev,
+                                                  ncap, want, w, *M);
+  else
+    zk::list_mark_k<<<nb, zk::TR_T, 0, st>>>(*t, rx, foff, flen, n_dev, ncap,
+                                             wslot, want, w);
   ZK_LAUNCH_CHECK();
   if (nbv > 0) {
     zk::list_sweep_k<false><<<nbv, zk::TR_T, 0, st>>>(*t, want, w, rec_off,
@@ -342,6 +386,40 @@ int zk_tree_list(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
                                             out);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+int zk_tree_list(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
+                 const int32_t* flen, const int64_t* n_dev, int64_t ncap,
+                 int32_t wslot, int64_t max_frame, int32_t* want, uint8_t* ws,
+                 int64_t ws_bytes, uint8_t* out, int64_t out_cap,
+                 int64_t* rec_off, int64_t* total, int32_t* err,
+                 int32_t terminate, hipStream_t st) {
+  return list_launch(t, rx, foff, flen, n_dev, ncap, wslot, nullptr,
+                     max_frame, want, ws, ws_bytes, out, out_cap, rec_off,
+                     total, err, terminate, st);
+}
+
+// zk_tree_list for the list frames of a session batch of any op mix: frame i
+// is served for segment f_seg[i] (zk_sess_split_segments' table of the list
+// class) — its watcher slot wslots[seg] arms a watch=1 list's child watch
+// (outside 0..63: none) — or refused as zk_sess.h sess_refusal says
+// (zk_sess_assign's seg_state / bad, nseg segments), header only.
+int zk_tree_list_sessions(const ZkTree* t, const uint8_t* rx,
+                          const int64_t* foff, const int32_t* flen,
+                          const int64_t* n_dev, int64_t ncap,
+                          const int32_t* f_seg, const int32_t* wslots,
+                          const int32_t* seg_state, const int64_t* bad,
+                          int64_t nseg, int64_t max_frame, int32_t* want,
+                          uint8_t* ws, int64_t ws_bytes, uint8_t* out,
+                          int64_t out_cap, int64_t* rec_off, int64_t* total,
+                          int32_t* err, int32_t terminate, hipStream_t st) {
+  if (f_seg == nullptr || wslots == nullptr || seg_state == nullptr ||
+      bad == nullptr || nseg < 1)
+    return -1;
+  const zk::SegTable M{f_seg, wslots, seg_state, bad, nseg};
+  return list_launch(t, rx, foff, flen, n_dev, ncap, -1, &M, max_frame, want,
+                     ws, ws_bytes, out, out_cap, rec_off, total, err,
+                     terminate, st);
 }
 
 }  // extern "C"

@@ -8,6 +8,9 @@
 //   sess_ranges_k      after the reply (and notification) encode: every
 //                      connection's slice of the reply stream, every
 //                      watcher's slice of the notification stream
+//   sess_split_seg_k   a batch of any op mix, after the split by engine class
+//                      (tree_mix.hip): a lane per frame carries its segment
+//                      to its place beside the class's compacted frame table
 //   sess_ev_hist_k,    the batch's watch events grouped by watcher slot,
 //   sess_ev_scatter_k  stable (request order inside a slot), in route.hip's
 //                      shape: a per-block histogram, the device-wide scan of
@@ -17,6 +20,7 @@
 //                      counter is shared.
 #include "zk_tree.h"
 #include "zk_sess.h"
+#include "zk_mix.h"
 #include "zk_session.h"
 
 namespace zk {
@@ -123,6 +127,26 @@ __global__ __launch_bounds__(SE_T) void sess_ranges_k(
     if (!(*ev_err & 2)) o = f >= 0 && f < ne ? ev_rec_off[f] : *ev_bytes;
     slot_off[s] = o;
   }
+}
+
+// f_seg_c[cls[i]][sub[i]] = f_seg[i] for the batch's frames (the split's cls /
+// sub, tree_mix.hip): the class tables c0 / c1 / c2, ncap entries each.  A row
+// the split's outputs do not bear out (sess_split_at) writes nothing.
+static_assert(MIX_CLASSES == 3, "sess_split_at: three class tables");
+__global__ __launch_bounds__(SE_T) void sess_split_seg_k(
+    const int32_t* __restrict__ f_seg, const int32_t* __restrict__ cls,
+    const int32_t* __restrict__ sub, const int64_t* __restrict__ n_dev,
+    int64_t ncap, int32_t* __restrict__ c0, int32_t* __restrict__ c1,
+    int32_t* __restrict__ c2) {
+  const int64_t i = (int64_t)blockIdx.x * SE_T + threadIdx.x;
+  const int64_t nd = *n_dev;
+  const int64_t nf = nd < ncap ? nd : ncap;
+  if (i < 0 || i >= nf) return;
+  const int32_t c = cls[i];
+  const int64_t j = sub[i];
+  if (sess_split_at(c, j, ncap) < 0) return;
+  int32_t* d = c == 0 ? c0 : c == 1 ? c1 : c2;
+  d[j] = f_seg[i];
 }
 
 // ---- event grouping ----------------------------------------------------------
@@ -243,6 +267,23 @@ int zk_sess_ranges(const int64_t* first, int64_t S, const int64_t* rec_off,
                       st>>>(first, S, rec_off, n_dev, ncap, total, err,
                             rep_off, slot_first, ev_rec_off, ev_count, ecap,
                             ev_bytes, ev_err, slot_off);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+// After zk_sess_assign (f_seg) and zk_tree_mix_split (cls / sub) of one frame
+// table (*n_dev frames, at most ncap): every frame's segment beside its
+// class's compacted frame table, f_seg_c0 / c1 / c2 [ncap] (written for the
+// class's frames).  One launch, no host read.
+int zk_sess_split_segments(const int32_t* f_seg, const int32_t* cls,
+                           const int32_t* sub, const int64_t* n_dev,
+                           int64_t ncap, int32_t* f_seg_c0, int32_t* f_seg_c1,
+                           int32_t* f_seg_c2, hipStream_t st) {
+  if (ncap < 0) return (int)hipErrorInvalidValue;
+  if (ncap == 0) return 0;
+  zk::sess_split_seg_k<<<(unsigned)((ncap + zk::SE_T - 1) / zk::SE_T),
+                         zk::SE_T, 0, st>>>(f_seg, cls, sub, n_dev, ncap,
+                                            f_seg_c0, f_seg_c1, f_seg_c2);
   ZK_LAUNCH_CHECK();
   return 0;
 }

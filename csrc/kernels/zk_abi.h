@@ -484,6 +484,26 @@ int zk_sess_group_events(const int32_t*, const int32_t*, const int64_t*,
                          const int32_t*, const int64_t*, int64_t, int64_t*,
                          int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
                          hipStream_t);
+// Session batches of any op mix.  zk_sess_split_segments: (f_seg, the
+// split's cls / sub, count, ncap) -> f_seg_c0 / c1 / c2 [ncap], each class's
+// frame -> segment.  zk_tree_list_sessions / zk_tree_acl_get_sessions:
+// zk_tree_list / zk_tree_acl_get with (the class's f_seg, wslots — the list
+// only —, seg_state, bad, S) after ncap, in place of the watcher slot.
+int zk_sess_split_segments(const int32_t*, const int32_t*, const int32_t*,
+                           const int64_t*, int64_t, int32_t*, int32_t*,
+                           int32_t*, hipStream_t);
+int zk_tree_list_sessions(const ZkTree*, const uint8_t*, const int64_t*,
+                          const int32_t*, const int64_t*, int64_t,
+                          const int32_t*, const int32_t*, const int32_t*,
+                          const int64_t*, int64_t, int64_t, int32_t*,
+                          uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
+                          int64_t*, int32_t*, int32_t, hipStream_t);
+int zk_tree_acl_get_sessions(const ZkTree*, const ZkAclTable*,
+                             const uint8_t*, const int64_t*, const int32_t*,
+                             const int64_t*, int64_t, const int32_t*,
+                             const int32_t*, const int64_t*, int64_t,
+                             uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
+                             int64_t*, int32_t*, int32_t, hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

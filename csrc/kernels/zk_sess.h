@@ -61,4 +61,50 @@ ZK_HD int32_t sess_boundary_bad(const int64_t* __restrict__ starts, int64_t S,
   return b;
 }
 
+// ---- a session batch of any op mix (GpuServer.serve_sessions_mixed) ---------
+// The list and GET_ACL engines' session instances (tree_list.hip,
+// tree_acl.hip) take a frame's segment from the table the split-segments
+// pass (tree_sess.hip sess_split_seg_k) compacted beside the class's frame
+// table.  What they and that pass decide from hostile tables is here.
+
+// Is v an index into a table of n entries?
+ZK_HD bool sess_in(int64_t v, int64_t n) { return v >= 0 && v < n; }
+
+// What a frame of segment `seg` is refused with before anything of it but
+// the xid is read: SYSTEMERROR when the table is unsound (*bad != 0) or the
+// segment is none of its S, SESSION_EXPIRED when its session is not alive
+// (seg_state[seg] == 1), else OK.  seg_state is read at an index in [0, S)
+// only.
+ZK_HD int32_t sess_refusal(const int64_t* __restrict__ bad,
+                           const int32_t* __restrict__ seg_state, int64_t S,
+                           int64_t seg) {
+  if (*bad != 0 || !sess_in(seg, S)) return ERR_SYSTEM;
+  return seg_state[seg] == 1 ? ERR_SESSION_EXPIRED : ERR_OK;
+}
+
+// The xid of a refused frame: what parse_request gives (0 for a body without
+// one).
+ZK_HD int32_t sess_xid(const uint8_t* __restrict__ buf, int64_t base,
+                       int64_t L) {
+  return L < 8 ? 0 : ld_be32(buf + base);
+}
+
+// The split-segments rule: frame i of class cls, index sub inside it, puts
+// its segment at f_seg_c[cls][sub], three tables of ncap entries.  A class
+// outside 0..2 or an index outside [0, ncap) has no place: -1; else the
+// place in the tables laid end to end, cls * ncap + sub.
+ZK_HD int64_t sess_split_at(int64_t cls, int64_t sub, int64_t ncap) {
+  if (!sess_in(cls, 3) || !sess_in(sub, ncap)) return -1;
+  return cls * ncap + sub;
+}
+
+// The segment table as the list and GET_ACL session instances read it.
+struct SegTable {
+  const int32_t* f_seg;      // [ncap] the class's frame -> segment
+  const int32_t* wslots;     // [S]
+  const int32_t* seg_state;  // [S] 0 serve, 1 session not alive
+  const int64_t* bad;        // [2] != 0: the table is unsound
+  int64_t S;
+};
+
 }  // namespace zk

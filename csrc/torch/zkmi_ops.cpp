@@ -1038,6 +1038,26 @@ void sess_group_events(const Tensor& ev_slot, const Tensor& ev_type,
          "sess_group_events");
 }
 
+// A session batch of any op mix: sess_assign's f_seg through tree_mix_split's
+// cls / sub -> the three classes' frame -> segment tables f_seg_c [3][ncap].
+void sess_split_segments(const Tensor& f_seg, const Tensor& cls,
+                         const Tensor& sub, const Tensor& n_dev, int64_t ncap,
+                         const std::vector<Tensor>& f_seg_c) {
+  const Tensor* d = &f_seg;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1,
+              "zkmi: sess_split_segments ncap");
+  need(f_seg_c, 3, "f_seg_c");
+  hip_ok(zk_sess_split_segments(
+             P<int32_t>(f_seg, I32, ncap, "f_seg"),
+             P<int32_t>(cls, I32, ncap, "cls", d),
+             P<int32_t>(sub, I32, ncap, "sub", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(f_seg_c[0], I32, ncap, "f_seg_c[0]", d),
+             P<int32_t>(f_seg_c[1], I32, ncap, "f_seg_c[1]", d),
+             P<int32_t>(f_seg_c[2], I32, ncap, "f_seg_c[2]", d), cur_stream()),
+         "sess_split_segments");
+}
+
 void watch_events(const Tensor& r_op, const Tensor& r_err, const Tensor& n_dev,
                   int64_t ncap, const Tensor& fired, const Tensor& bsum,
                   const Tensor& ev_slot, const Tensor& ev_type,
@@ -1299,6 +1319,48 @@ void tree_list(const std::vector<Tensor>& t, const Tensor& rx,
          "tree_list");
 }
 
+// tree_list for the list class of a session batch of any op mix: the class's
+// f_seg (sess_split_segments), the segments' wslots, sess_assign's seg_state
+// and bad in place of the watcher slot.
+void tree_list_sessions(const std::vector<Tensor>& t, const Tensor& rx,
+                        const Tensor& foff, const Tensor& flen,
+                        const Tensor& n_dev, int64_t ncap,
+                        const Tensor& f_seg, const Tensor& wslots,
+                        const Tensor& seg_state, const Tensor& bad,
+                        int64_t max_frame, const Tensor& want,
+                        const Tensor& ws, const Tensor& out, int64_t out_cap,
+                        const Tensor& rec_off, const Tensor& total,
+                        const Tensor& err, bool terminate) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  const int64_t S = wslots.numel();
+  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1,
+              "zkmi: tree_list_sessions ncap");
+  TORCH_CHECK(max_frame >= 0, "zkmi: tree_list_sessions max_frame");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_list_sessions out_cap");
+  uint8_t* w = P<uint8_t>(ws, U8, zk_tree_list_workspace(ncap),
+                          "list workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w) % 16 == 0,
+              "zkmi: list workspace must be 16-byte aligned");
+  hip_ok(zk_tree_list_sessions(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
+             P<int32_t>(wslots, I32, S, "wslots", d),
+             P<int32_t>(seg_state, I32, S, "seg_state", d),
+             P<int64_t>(bad, I64, 2, "bad", d), S, max_frame,
+             P<int32_t>(want, I32, s.store.cap, "want", d), w, ws.numel(),
+             P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_list_sessions");
+}
+
 // The ACL path (tree_acl.hip).  acl: the table's tensor list (acl_table);
 // one workspace of tree_acl_workspace(ncap) bytes serves both ops.
 int64_t tree_acl_workspace(int64_t n) {
@@ -1365,6 +1427,42 @@ void tree_acl_get(const std::vector<Tensor>& t,
              P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
              cur_stream()),
          "tree_acl_get");
+}
+
+// tree_acl_get for the GET_ACL class of a session batch of any op mix: the
+// class's f_seg (sess_split_segments), sess_assign's seg_state [S] and bad.
+void tree_acl_get_sessions(const std::vector<Tensor>& t,
+                           const std::vector<Tensor>& acl, const Tensor& rx,
+                           const Tensor& foff, const Tensor& flen,
+                           const Tensor& n_dev, int64_t ncap,
+                           const Tensor& f_seg, const Tensor& seg_state,
+                           const Tensor& bad, const Tensor& ws,
+                           const Tensor& out, int64_t out_cap,
+                           const Tensor& rec_off, const Tensor& total,
+                           const Tensor& err, bool terminate) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a = acl_table(acl, d);
+  const int64_t S = seg_state.numel();
+  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+              " elements, needs ", s.store.cap);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 28), "zkmi: tree_acl ncap");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_acl_get_sessions out_cap");
+  hip_ok(zk_tree_acl_get_sessions(
+             &s, &a, P<uint8_t>(rx, U8, 1, "rx", d),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
+             P<int32_t>(seg_state, I32, S, "seg_state", d),
+             P<int64_t>(bad, I64, 2, "bad", d), S, acl_ws(ws, ncap, d),
+             ws.numel(), P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_acl_get_sessions");
 }
 
 // Mixed batches (tree_mix.hip): the split of a batch's frame table by engine
@@ -1869,6 +1967,9 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor ev_plen, Tensor ev_total, Tensor(a!) ws, Tensor(b!) g_slot, "
         "Tensor(c!) g_type, Tensor(d!) g_poff, Tensor(e!) g_plen, "
         "Tensor(f!) slot_first) -> ()", &sess_group_events);
+  m.def("sess_split_segments(Tensor f_seg, Tensor cls, Tensor sub, "
+        "Tensor count, int ncap, Tensor(a!)[] f_seg_c) -> ()",
+        &sess_split_segments);
   m.def("tree_seq_workspace(int n) -> int", &tree_seq_workspace);
   m.def("tree_seq_zeroed(int n) -> int", &tree_seq_zeroed);
   m.def("tree_seq_debug(Tensor buf) -> ()", &tree_seq_debug);
@@ -1896,6 +1997,13 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
         "bool terminate=False) -> ()",
         &tree_list);
+  m.def("tree_list_sessions(Tensor(a!)[] tree, Tensor rx, Tensor frame_off, "
+        "Tensor frame_len, Tensor count, int ncap, Tensor f_seg, "
+        "Tensor wslots, Tensor seg_state, Tensor bad, int max_frame, "
+        "Tensor(b!) want, Tensor(c!) ws, Tensor(d!) out, int out_cap, "
+        "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
+        "bool terminate=False) -> ()",
+        &tree_list_sessions);
   m.def("tree_mix_split_workspace(int n) -> int", &tree_mix_split_workspace);
   m.def("tree_mix_merge_workspace(int n) -> int", &tree_mix_merge_workspace);
   m.def("tree_mix_small() -> int", &tree_mix_small);
@@ -1919,6 +2027,12 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(a!) ws, Tensor(b!) out, int out_cap, Tensor(c!) rec_off, "
         "Tensor(d!) total, Tensor(e!) err, bool terminate=False) -> ()",
         &tree_acl_get);
+  m.def("tree_acl_get_sessions(Tensor[] tree, Tensor[] acl, Tensor rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor f_seg, Tensor seg_state, Tensor bad, Tensor(a!) ws, "
+        "Tensor(b!) out, int out_cap, Tensor(c!) rec_off, Tensor(d!) total, "
+        "Tensor(e!) err, bool terminate=False) -> ()",
+        &tree_acl_get_sessions);
   m.def("watch_events(Tensor r_op, Tensor r_err, Tensor count, int ncap, "
         "Tensor fired, Tensor(a!) bsum, Tensor(b!) ev_slot, "
         "Tensor(c!) ev_type, Tensor(d!) ev_path_off, Tensor(e!) ev_path_len, "

@@ -649,6 +649,17 @@ class _SegState(object):
         self.rep_off = torch.zeros(S + 1, dtype=I64, device=dev)
         self.state = torch.zeros(S, dtype=I32, device=dev)
         self.bad = torch.zeros(2, dtype=I64, device=dev)
+        self.f_seg_c = None               # per engine class (lazy)
+
+    def class_tables(self):
+        """``f_seg`` through the split of a batch of any op mix
+        (:meth:`GpuServer.serve_sessions_mixed`): three int32 [cap_frames]
+        tables, class c's frame -> segment; allocated on first use."""
+        if self.f_seg_c is None:
+            cap = int(self.f_seg.numel())
+            buf = torch.zeros(3 * cap, dtype=I32, device=self.f_seg.device)
+            self.f_seg_c = [buf[c * cap:(c + 1) * cap] for c in range(3)]
+        return self.f_seg_c
 
 
 class GpuServer(object):
@@ -1053,10 +1064,12 @@ class GpuServer(object):
         way leaves a gap in its parent's cversion, as any failed numbered
         create does.)
 
-        Single-session still: the list ops, GET_ACL and mixed batches
-        (:meth:`serve_list`, :meth:`serve_acl`, :meth:`serve_mixed`) and the
-        SET_WATCHES catch-up — a SET_WATCHES frame here gets its header-only
-        reply and no catch-up.  How a connection's notification slice is
+        The list ops and GET_ACL are not served here (UNIMPLEMENTED): a
+        session batch that mixes them in goes through
+        :meth:`serve_sessions_mixed`.  Single-session still: the ordered
+        mixed batch and the SET_WATCHES catch-up — a SET_WATCHES frame here
+        gets its header-only reply and no catch-up.  How a connection's
+        notification slice is
         interleaved with its reply slice on the socket is the front end's
         business."""
         L = _lib.lib()
@@ -1126,7 +1139,8 @@ class GpuServer(object):
         return self.result
 
     def session_stats(self):
-        """Of the last :meth:`serve_sessions` (one host read): ``bad`` (torn
+        """Of the last :meth:`serve_sessions` or
+        :meth:`serve_sessions_mixed` (one host read): ``bad`` (torn
         frames + faults of the segment table; not 0: the batch was refused),
         ``first_bad_segment`` (-1: none) and ``expired_segments`` (segments
         whose session the table did not hold alive)."""
@@ -1371,6 +1385,157 @@ class GpuServer(object):
             terminate)
         self.last_rec_off = self.mix_rec_off[1]
         self.result = (out, total, err, ft)
+        return self.result
+
+    def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
+                             max_frame=None, out=None):
+        """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
+        connections of :class:`SessionSegments` ``segs``, whatever ops they
+        mix, as ONE batch: :meth:`serve_sessions` for every op of
+        :meth:`serve_mixed`.  ``rx``, ``n``, ``segs`` and ``table`` as in
+        :meth:`serve_sessions`; ``max_frame`` and ``out`` (default
+        ``self.mix_out``) as in :meth:`serve_mixed`.  Returns ``(out, total,
+        err, frame table)`` with the whole batch's frame table, and leaves
+        ``self.seg`` (``f_seg``, ``first``, ``rep_off``, ``state``, ``bad``),
+        ``self.notif``, ``self.notif_slots`` and ``self.last_rec_off`` (the
+        merged frame starts) as those two do.  Nothing is read back, nothing
+        is allocated after the first call (of a segment count), and the call
+        can be captured on one stream where :meth:`serve_mixed` can.
+
+        The batch contract.  One K1 scan and one segment assign over the
+        whole frame table; the split of :meth:`serve_mixed`, the frames'
+        segments carried through it (csrc/kernels/tree_sess.hip
+        sess_split_seg_k); the engines in :meth:`serve_mixed`'s fixed order —
+        serve (unordered), GET_ACL, list — each over its class's frames in
+        request order, each frame for its own segment's session and watcher
+        slot.  So a list or a GET_ACL from any connection sees the tree
+        after all writes of the batch, from every connection.  A ``watch=1``
+        list arms the child watch of its own segment's ``wslots[s]``, after
+        the batch's writes (they do not fire it); a value outside 0..63 arms
+        nothing.  ``self.seg.rep_off[s]`` slices the merged stream:
+        connection s's replies are ``out[rep_off[s]:rep_off[s + 1]]``;
+        ``notif_buf[slot_off[w]:slot_off[w + 1]]`` is watcher w's
+        notifications, in request order.
+
+        Refusals.  An unsound table (``bad != 0``: a torn frame, a
+        ``starts`` that does not begin at 0 or descends) answers every
+        request of the batch SYSTEMERROR, list and GET_ACL frames included;
+        a segment whose session ``table`` does not hold alive has all its
+        requests answered SESSION_EXPIRED.  For the list and ACL engines
+        both are header-only replies with the xid the engine parsed: a
+        refused frame looks nothing up, claims no parent and arms nothing.
+        Refusal takes precedence over BAD_ARGUMENTS and UNIMPLEMENTED, as in
+        the serve.
+
+        ``err`` and overflow follow :meth:`serve_mixed`'s rule: the first
+        non-zero one of the three engines' encoders, else 2 when the merged
+        stream does not fit ``out``; then ``total`` is 0, ``out`` is
+        untouched and ``rep_off`` is all zero.  On a tree without an ACL
+        table GET_ACL goes to the serve (UNIMPLEMENTED), as in
+        :meth:`serve_mixed`.
+
+        Not offered: in-batch ordering (``serve_sessions(ordered=True)``)
+        and the SET_WATCHES catch-up — a SET_WATCHES frame gets its
+        header-only reply, as in :meth:`serve_sessions`.
+
+        Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
+        and on a sharded tree, as the two entry points do."""
+        L = _lib.lib()
+        tree = self.tree
+        if self.fused_rows or self.read_only:
+            raise ValueError('serve_sessions_mixed: no session form of the '
+                             'read-only or the fused-rows serve')
+        if tree.shard is not None and tree.shard[1] > 1:
+            raise ValueError('serve_sessions_mixed: a sharded tree does not '
+                             'index every child of its parents')
+        if not isinstance(segs, SessionSegments):
+            raise TypeError('serve_sessions_mixed: segs is a SessionSegments')
+        self._mix_buffers()
+        cap = self.cap_frames
+        if self.seg is None or self.seg.S != segs.S:
+            self.seg = _SegState(cap, segs.S, tree.device)
+        sg = self.seg
+        seg_c = sg.class_tables()
+        if out is None:
+            out = self.mix_out
+        if max_frame is None:
+            max_frame = consts.MAX_PACKET
+        ft = self.scanner.scan(rx, n)
+        _lib.sess_assign(
+            ft.off, ft.length, ft.count, cap, segs.starts, segs.sessions,
+            sg.f_seg, sg.first, sg.state, sg.bad,
+            table=None if table is None else table._tensors,
+            server_id=0 if table is None else table.server_id,
+            span=0 if table is None else table.span)
+        _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
+                            tree.acl is not None, self.mix_cls, self.mix_sub,
+                            self.mix_foff, self.mix_flen, self.mix_counts,
+                            self.mix_split_ws)
+        _lib.sess_split_segments(sg.f_seg, self.mix_cls, self.mix_sub,
+                                 ft.count, cap, seg_c)
+        fa, fc, fl = self.mix_frames
+        # the serve's class, as serve_sessions serves a batch
+        r = self.resp
+        r.count = fa.count
+        rout = [r.opcode, r.xid, r.err, r.node, r.zxid, r.path_off,
+                r.path_len, r.slot, self.presized[0], self.presized[1]]
+        now = int(time.time() * 1000)
+        seqno = self._seq_order(rx, fa) if self.seq_order else None
+        fired = self.fired if tree.watch is not None else None
+        _lib.tree_serve_frames_sessions(
+            tree.tensors, rx, fa.off, fa.length, fa.count, cap, rout, now,
+            fired, seqno, seg_c[0], segs.sessions, segs.wslots, sg.state,
+            sg.bad)
+        L.tree_finish_scan(tree.tensors, fa.count, 0, True, cap,
+                           self.presized[1], self.total_err[0])
+        if tree.acl is not None:
+            _lib.tree_acl_record(tree.acl, rx, fa.off, fa.length, fa.count,
+                                 cap, r.opcode, r.err, r.node,
+                                 self._acl_workspace())
+        a_out, _, a_total, a_err = B.encode_responses(
+            r, tree.store, self.out.numel(), out=self.out,
+            presized=self.presized, terminate=False,
+            total_err=self.total_err, prescanned=True,
+            rec_off=self.mix_rec_off[0])
+        if tree.compact_free:
+            tree.free_compact()
+        # the two read engines, after the batch's writes
+        c_out, l_out = self.mix_scratch
+        c_total, c_err = self.acl_total_err
+        if tree.acl is not None:
+            _lib.tree_acl_get_sessions(
+                tree.tensors, tree.acl, rx, fc.off, fc.length, fc.count, cap,
+                seg_c[1], sg.state, sg.bad, self._acl_workspace(), c_out,
+                c_out.numel(), self.acl_rec_off, c_total, c_err, False)
+        else:
+            c_out = l_out
+        l_total, l_err = self.list_total_err
+        _lib.tree_list_sessions(
+            tree.tensors, rx, fl.off, fl.length, fl.count, cap, seg_c[2],
+            segs.wslots, sg.state, sg.bad, max_frame, self.list_want,
+            self.list_ws, l_out, l_out.numel(), self.list_rec_off, l_total,
+            l_err, False)
+        total, err = self.mix_total_err
+        _lib.tree_mix_merge(
+            self.mix_cls, self.mix_sub, ft.count, self.mix_counts, cap,
+            [a_out, c_out, l_out],
+            [self.mix_rec_off[0], self.acl_rec_off, self.list_rec_off],
+            [a_total, c_total, l_total], [a_err, c_err, l_err], out,
+            out.numel(), self.mix_rec_off[1], total, err, self.mix_merge_ws,
+            terminate)
+        rec_off = self.mix_rec_off[1]
+        self.last_rec_off = rec_off
+        self.result = (out, total, err, ft)
+        if tree.watch is not None:
+            self._notify_grouped()
+            g = self._grouped
+            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
+                             sg.rep_off, g['first'], g['rec_off'],
+                             self.ev_total[0:1], g['total_err'][0],
+                             g['total_err'][1], g['off'])
+        else:
+            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
+                             sg.rep_off)
         return self.result
 
     def acl_stats(self):

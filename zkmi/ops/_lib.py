@@ -336,5 +336,40 @@ def sess_group_events(ev_slot, ev_type, ev_poff, ev_plen, ev_total, ws,
                             g_slot, g_type, g_poff, g_plen, slot_first)
 
 
+def sess_split_segments(f_seg, cls, sub, count, ncap, f_seg_c):
+    """A session batch of any op mix, after :func:`sess_assign` (``f_seg``)
+    and :func:`tree_mix_split` (``cls`` / ``sub``) of one frame table:
+    ``f_seg_c[cls[i]][sub[i]] = f_seg[i]`` for every frame of the batch, so
+    each engine finds a frame's segment beside its compacted frame table.
+    ``f_seg_c``: three int32 [ncap] tensors.  One launch, no host read."""
+    lib().sess_split_segments(f_seg, cls, sub, count, int(ncap),
+                              list(f_seg_c))
+
+
+def tree_list_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
+                       wslots, seg_state, bad, max_frame, want, ws, out,
+                       out_cap, rec_off, total, err, terminate=False):
+    """:func:`tree_list` for the list class of a session batch of any op mix:
+    frame i is served for segment ``f_seg[i]`` (its ``watch=1`` arms the
+    child watch of ``wslots[f_seg[i]]``; outside 0..63: none); with
+    ``bad[0] != 0`` every frame is refused SYSTEMERROR, a segment with state
+    :data:`SEG_EXPIRED` SESSION_EXPIRED, header only and without effect."""
+    lib().tree_list_sessions(tree, rx, frame_off, frame_len, count, int(ncap),
+                             f_seg, wslots, seg_state, bad, int(max_frame),
+                             want, ws, out, int(out_cap), rec_off, total, err,
+                             bool(terminate))
+
+
+def tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count, ncap,
+                          f_seg, seg_state, bad, ws, out, out_cap, rec_off,
+                          total, err, terminate=False):
+    """:func:`tree_acl_get` for the GET_ACL class of a session batch of any
+    op mix; refusals as :func:`tree_list_sessions`."""
+    lib().tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count,
+                                int(ncap), f_seg, seg_state, bad, ws, out,
+                                int(out_cap), rec_off, total, err,
+                                bool(terminate))
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
