@@ -504,6 +504,20 @@ int zk_tree_acl_get_sessions(const ZkTree*, const ZkAclTable*,
                              const int32_t*, const int64_t*, int64_t,
                              uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
                              int64_t*, int32_t*, int32_t, hipStream_t);
+// The SET_WATCHES catch-up of a session batch (tree_resume.hip; the rules:
+// zk_resume.h), after its serve: (tree, rx, its length, frames off / len,
+// count, ncap, f_seg, wslots, seg_state, bad, S, workspace, ecap) -> the
+// events in stream order (ev_slot / type / poff / plen [ecap], ev_total[2]),
+// grouped by watcher slot (g_* [ecap], slot_first[65]) and stats[8].  The
+// workspace: int64 words for (ncap, ecap).
+int64_t zk_watch_resume_sessions_workspace(int64_t ncap, int64_t ecap);
+int zk_watch_resume_sessions(const ZkTree*, const uint8_t*, int64_t,
+                             const int64_t*, const int32_t*, const int64_t*,
+                             int64_t, const int32_t*, const int32_t*,
+                             const int32_t*, const int64_t*, int64_t,
+                             int64_t*, int64_t, int32_t*, int32_t*, int64_t*,
+                             int32_t*, int64_t*, int32_t*, int32_t*, int64_t*,
+                             int32_t*, int64_t*, int64_t*, hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

@@ -1102,6 +1102,60 @@ void watch_resume(const std::vector<Tensor>& t, const Tensor& rx,
          "watch_resume");
 }
 
+int64_t watch_resume_sessions_workspace(int64_t ncap, int64_t ecap) {
+  TORCH_CHECK(ncap >= 1 && ecap >= 1,
+              "zkmi: watch_resume_sessions_workspace ncap, ecap >= 1");
+  return zk_watch_resume_sessions_workspace(ncap, ecap);
+}
+
+// The SET_WATCHES catch-up of a session batch (tree_resume.hip): ev / grouped
+// = [slot, type, path_off, path_len], ecap = their length.
+void watch_resume_sessions(const std::vector<Tensor>& t, const Tensor& rx,
+                           const Tensor& foff, const Tensor& flen,
+                           const Tensor& n_dev, int64_t ncap,
+                           const Tensor& f_seg, const Tensor& wslots,
+                           const Tensor& seg_state, const Tensor& bad,
+                           const Tensor& ws, const std::vector<Tensor>& ev,
+                           const Tensor& ev_total,
+                           const std::vector<Tensor>& grouped,
+                           const Tensor& slot_first, const Tensor& stats) {
+  ZkTree s = tree(t);
+  TORCH_CHECK(s.wt_key != nullptr,
+              "zkmi: watch_resume_sessions needs a watch table");
+  const Tensor* d = &t[0];
+  need(ev, 4, "ev");
+  need(grouped, 4, "grouped");
+  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1,
+              "zkmi: watch_resume_sessions ncap");
+  const int64_t S = wslots.numel();
+  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  const int64_t ecap = ev[0].numel();
+  TORCH_CHECK(ecap >= 1, "zkmi: watch_resume_sessions: no room for an event");
+  hip_ok(zk_watch_resume_sessions(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
+             P<int32_t>(wslots, I32, S, "wslots", d),
+             P<int32_t>(seg_state, I32, S, "seg_state", d),
+             P<int64_t>(bad, I64, 2, "bad", d), S,
+             P<int64_t>(ws, I64, zk_watch_resume_sessions_workspace(ncap, ecap),
+                        "workspace", d),
+             ecap, P<int32_t>(ev[0], I32, ecap, "ev_slot", d),
+             P<int32_t>(ev[1], I32, ecap, "ev_type", d),
+             P<int64_t>(ev[2], I64, ecap, "ev_path_off", d),
+             P<int32_t>(ev[3], I32, ecap, "ev_path_len", d),
+             P<int64_t>(ev_total, I64, 2, "ev_total", d),
+             P<int32_t>(grouped[0], I32, ecap, "g_slot", d),
+             P<int32_t>(grouped[1], I32, ecap, "g_type", d),
+             P<int64_t>(grouped[2], I64, ecap, "g_path_off", d),
+             P<int32_t>(grouped[3], I32, ecap, "g_path_len", d),
+             P<int64_t>(slot_first, I64, 65, "slot_first", d),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "watch_resume_sessions");
+}
+
 // Clear watcher slot wslot's bit from every mask of the tree's watch table.
 void watch_drop(const std::vector<Tensor>& t, int64_t wslot) {
   ZkTree s = tree(t);
@@ -2041,6 +2095,14 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor frame_len, Tensor count, int ncap, int wslot, "
         "Tensor(b!) ent, Tensor(c!) ev_type, Tensor(d!) ev_path_off, "
         "Tensor(e!) ev_path_len, Tensor(f!) out) -> ()", &watch_resume);
+  m.def("watch_resume_sessions_workspace(int ncap, int ecap) -> int",
+        &watch_resume_sessions_workspace);
+  m.def("watch_resume_sessions(Tensor(a!)[] tree, Tensor rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor f_seg, Tensor wslots, Tensor seg_state, Tensor bad, "
+        "Tensor(b!) ws, Tensor(c!)[] ev, Tensor(d!) ev_total, "
+        "Tensor(e!)[] grouped, Tensor(f!) slot_first, Tensor(g!) stats) "
+        "-> ()", &watch_resume_sessions);
   m.def("watch_drop(Tensor(a!)[] tree, int wslot) -> ()", &watch_drop);
   m.def("watch_rebuild(Tensor(a!)[] tree, Tensor old_key, Tensor old_mask) "
         "-> ()", &watch_rebuild);

@@ -720,6 +720,9 @@ class GpuServer(object):
         self.seg = None                   # the last session batch's segments
         self.notif_slots = None           # (slot_first, slot_off) of its
         self._grouped = None              # notifications (buffers: lazy)
+        self.resume_notif = None          # the last SET_WATCHES catch-up
+        self.resume_slots = None          # (slot_first, slot_off) of a
+        self._rs = None                   # session batch's (buffers: lazy)
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -1033,8 +1036,80 @@ class GpuServer(object):
         self.notif = (out, total, g['slot'], self.ev_total[0:1])
         self.notif_slots = (g['first'], g['off'])
 
+    def _resume_sessions(self, rx, ft, segs, rec_off, total, err):
+        """The SET_WATCHES catch-up of the session batch just served
+        (csrc/kernels/tree_resume.hip; the rules: zk_resume.h): every
+        SET_WATCHES frame of ``ft`` for its own segment's watcher slot,
+        against the tree as the batch left it.  Leaves ``self.resume_notif``
+        and ``self.resume_slots``; nothing is read back.  The buffers are
+        allocated on first use and grown when a larger ``rx`` comes."""
+        dev = self.tree.device
+        sg = self.seg
+        # a listed path takes at least the 4 bytes of its length in its
+        # frame: no batch lists more paths than its bytes / 4, so the entry
+        # and the event room (ecap of each) cannot overflow
+        need = max(1, int(rx.numel()) // 4)
+        b = self._rs
+        if b is None or b['ecap'] < need:
+            ecap = need
+            rec = lambda: [torch.zeros(ecap, dtype=I32, device=dev),
+                           torch.zeros(ecap, dtype=I32, device=dev),
+                           torch.zeros(ecap, dtype=I64, device=dev),
+                           torch.zeros(ecap, dtype=I32, device=dev)]
+            b = {'ecap': ecap, 'ev': rec(), 'g': rec(),
+                 'ev_total': torch.zeros(2, dtype=I64, device=dev),
+                 'ws': torch.empty(_lib.watch_resume_sessions_workspace(
+                     self.cap_frames, ecap), dtype=I64, device=dev),
+                 'first': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                      device=dev),
+                 'off': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                    device=dev),
+                 'stats': torch.zeros(8, dtype=I64, device=dev),
+                 'total_err': B._total_err(dev),
+                 'rec_off': torch.zeros(ecap, dtype=I64, device=dev),
+                 # as _resume sizes it: 32 bytes of frame around a path, and
+                 # the paths are the request's own bytes (rx <= 4 ecap + 3)
+                 'buf': torch.empty(ecap * 32 + 4 * ecap + 4 + 64, dtype=U8,
+                                    device=dev)}
+            g = b['g']
+            b['resp'] = self._notif_batch(g[2], g[3], rx, g[1],
+                                          b['ev_total'][0:1], ecap, dev)
+            self._rs = b
+        b['resp'].path_arena = rx           # the encode arena: the requests
+        _lib.watch_resume_sessions(
+            self.tree.tensors, rx, ft.off, ft.length, ft.count,
+            self.cap_frames, sg.f_seg, segs.wslots, sg.state, sg.bad, b['ws'],
+            b['ev'], b['ev_total'], b['g'], b['first'], b['stats'])
+        out, _, rtotal, rerr = B.encode_responses(
+            b['resp'], self.tree.store, b['buf'].numel(), out=b['buf'],
+            total_err=b['total_err'], rec_off=b['rec_off'])
+        _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames, total,
+                         err, sg.rep_off, b['first'], b['rec_off'],
+                         b['ev_total'][0:1], b['total_err'][0],
+                         b['total_err'][1], b['off'])
+        self.resume_notif = (out, rtotal, b['g'][0], b['ev_total'][0:1])
+        self.resume_slots = (b['first'], b['off'])
+
+    def resume_stats(self):
+        """Of the last session batch served with ``resume=True`` (one host
+        read): ``events`` the catch-up found and ``events_written`` (fewer:
+        the event room overflowed), watches ``rearmed``, paths ``listed`` by
+        the frames that were caught up, ``dropped`` (listed paths past the
+        entry room, neither answered nor re-armed), ``no_slot`` (paths of
+        live SET_WATCHES frames whose segment's watcher slot is outside
+        0..63) and ``encode_err`` (the catch-up encoder's flag; 2:
+        the notification buffer is too small)."""
+        b = self._rs
+        if b is None:
+            raise ValueError('resume_stats: no session batch was resumed')
+        v = torch.cat([b['stats'][:len(_lib.RESUME_STATS)],
+                       b['total_err'][1].to(I64)]).cpu().tolist()
+        st = dict(zip(_lib.RESUME_STATS, v))
+        st['encode_err'] = v[-1]
+        return st
+
     def serve_sessions(self, rx, n, segs, ordered=False, passes=4,
-                       terminate=False, table=None):
+                       terminate=False, table=None, resume=False):
         """Serve ``rx[:n]``, the concatenated whole frames of the
         ``segs.S`` connections of :class:`SessionSegments` ``segs``, as ONE
         batch: one K1 scan and one serve (``passes`` of them when
@@ -1067,11 +1142,51 @@ class GpuServer(object):
         The list ops and GET_ACL are not served here (UNIMPLEMENTED): a
         session batch that mixes them in goes through
         :meth:`serve_sessions_mixed`.  Single-session still: the ordered
-        mixed batch and the SET_WATCHES catch-up — a SET_WATCHES frame here
-        gets its header-only reply and no catch-up.  How a connection's
-        notification slice is
+        mixed batch.  How a connection's notification slices are
         interleaved with its reply slice on the socket is the front end's
-        business."""
+        business.
+
+        ``resume``: the SET_WATCHES catch-up (csrc/kernels/tree_resume.hip),
+        on a tree with a watch table (``ValueError`` without one).  Off, a
+        SET_WATCHES frame gets its header-only reply and nothing else.  On,
+        the reply is the same and every SET_WATCHES frame of the batch is
+        caught up for its own segment's watcher slot ``wslots[s]`` by the
+        session rule of :meth:`serve`'s ``resume`` (a listed data watch:
+        node gone NodeDeleted, mzxid > relZxid NodeDataChanged, else
+        re-armed; an exist watch: node there NodeCreated, else re-armed; a
+        child watch: node gone NodeDeleted, pzxid > relZxid
+        NodeChildrenChanged, else re-armed), each frame with its own
+        relZxid, any number of them anywhere in a segment.  The catch-up
+        reads the tree as the batch leaves it: it is as if every SET_WATCHES
+        frame of the batch came after all its other frames, in stream order
+        among themselves — so a write by another connection of the batch to
+        a listed path is an event of the catch-up when its zxid is past the
+        frame's relZxid, and never fires the re-armed watch (as
+        ``serve(resume=True)`` treats the writes of its own batch).  Nothing
+        is caught up, re-armed or sent for a refused batch, a segment whose
+        session is not alive, a frame of no segment, a segment whose
+        ``wslots`` value is outside 0..63 (its paths are counted ``no_slot``)
+        or a frame that is not a well-formed SET_WATCHES.  It leaves, with no
+        host read,
+
+        ``self.resume_notif``  ``(buf, total, slots, count)``: the catch-up's
+                               xid -1 frames grouped by watcher slot, inside
+                               a slot in stream order (frame order, then the
+                               data, exist and child lists, then list
+                               order); the paths are the request's own bytes.
+                               Apart from ``self.notif``, which stays the
+                               batch's write-fired events;
+        ``self.resume_slots``  ``(slot_first, slot_off)``, both [65]: watcher
+                               w's catch-up is ``buf[slot_off[w]:slot_off[w +
+                               1]]``.  A front end writes that slice before
+                               the slot's slice of ``self.notif``: what the
+                               catch-up reports happened before the batch's
+                               re-armed watches could fire;
+
+        and :meth:`resume_stats` reads its counters.  Its buffers are sized
+        from ``rx.numel()``, allocated on first use and grown when a larger
+        ``rx`` comes; a call that does not grow them is capturable where the
+        call without ``resume`` is."""
         L = _lib.lib()
         if self.fused_rows or self.read_only:
             raise ValueError('serve_sessions: no session form of the '
@@ -1079,6 +1194,8 @@ class GpuServer(object):
         if not isinstance(segs, SessionSegments):
             raise TypeError('serve_sessions: segs is a SessionSegments')
         tree = self.tree
+        if resume and tree.watch is None:
+            raise ValueError('serve_sessions: resume needs a watch table')
         if self.seg is None or self.seg.S != segs.S:
             self.seg = _SegState(self.cap_frames, segs.S, tree.device)
         sg = self.seg
@@ -1133,6 +1250,8 @@ class GpuServer(object):
                              total, err, sg.rep_off, g['first'],
                              g['rec_off'], self.ev_total[0:1],
                              g['total_err'][0], g['total_err'][1], g['off'])
+            if resume:
+                self._resume_sessions(rx, ft, segs, rec_off, total, err)
         else:
             _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
                              total, err, sg.rep_off)
@@ -1388,7 +1507,7 @@ class GpuServer(object):
         return self.result
 
     def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
-                             max_frame=None, out=None):
+                             max_frame=None, out=None, resume=False):
         """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
         connections of :class:`SessionSegments` ``segs``, whatever ops they
         mix, as ONE batch: :meth:`serve_sessions` for every op of
@@ -1434,9 +1553,17 @@ class GpuServer(object):
         table GET_ACL goes to the serve (UNIMPLEMENTED), as in
         :meth:`serve_mixed`.
 
-        Not offered: in-batch ordering (``serve_sessions(ordered=True)``)
-        and the SET_WATCHES catch-up — a SET_WATCHES frame gets its
-        header-only reply, as in :meth:`serve_sessions`.
+        ``resume``: the SET_WATCHES catch-up, as in :meth:`serve_sessions`
+        (``self.resume_notif``, ``self.resume_slots``, :meth:`resume_stats`;
+        ``ValueError`` on a tree without a watch table).  It runs once over
+        the whole frame table and its segments, after the three engines: the
+        tree it reads is the one the whole batch leaves, a listed path that
+        any connection of the batch wrote is an event of the catch-up and
+        never hits the re-armed watch, and a ``watch=1`` list of the batch is
+        armed before it.  Off, a SET_WATCHES frame gets its header-only
+        reply and nothing else; on, the replies are the same.
+
+        Not offered: in-batch ordering (``serve_sessions(ordered=True)``).
 
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
@@ -1450,6 +1577,9 @@ class GpuServer(object):
                              'index every child of its parents')
         if not isinstance(segs, SessionSegments):
             raise TypeError('serve_sessions_mixed: segs is a SessionSegments')
+        if resume and tree.watch is None:
+            raise ValueError('serve_sessions_mixed: resume needs a watch '
+                             'table')
         self._mix_buffers()
         cap = self.cap_frames
         if self.seg is None or self.seg.S != segs.S:
@@ -1533,6 +1663,8 @@ class GpuServer(object):
                              sg.rep_off, g['first'], g['rec_off'],
                              self.ev_total[0:1], g['total_err'][0],
                              g['total_err'][1], g['off'])
+            if resume:
+                self._resume_sessions(rx, ft, segs, rec_off, total, err)
         else:
             _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
                              sg.rep_off)

@@ -371,5 +371,41 @@ def tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count, ncap,
                                 bool(terminate))
 
 
+# the SET_WATCHES catch-up of a session batch (csrc/kernels/tree_resume.hip;
+# the rules: zk_resume.h)
+RESUME_CHUNK = 1024     # bytes of a frame staged through LDS at a time: chunk
+                        # c of a frame covers rx[c0 + c * RESUME_CHUNK, ...),
+                        # c0 = the list start (frame body + 16) rounded down
+                        # to 16 (rx itself 16-aligned); zk_resume.h RS_CHUNK
+RESUME_STATS = ('events', 'events_written', 'rearmed', 'listed', 'dropped',
+                'no_slot')
+
+
+def watch_resume_sessions_workspace(ncap, ecap):
+    """int64 words of :func:`watch_resume_sessions`' workspace for ``ncap``
+    frames and ``ecap`` listed paths (nothing in it needs zeroing)."""
+    return lib().watch_resume_sessions_workspace(int(ncap), int(ecap))
+
+
+def watch_resume_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
+                          wslots, seg_state, bad, ws, ev, ev_total, grouped,
+                          slot_first, stats):
+    """The SET_WATCHES catch-up of a session batch, after its serve and on
+    the current stream: every SET_WATCHES frame of the frame table is caught
+    up for watcher slot ``wslots[f_seg[i]]`` against the tree as it is now.
+    ``ev`` and ``grouped``: [slot int32, type int32, path_off int64, path_len
+    int32], each ``ecap`` long (path offsets into ``rx``) — the events in
+    stream order and grouped by watcher slot (``slot_first`` int64 [65], as
+    :func:`sess_group_events`); ``ev_total`` int64 [2] (written, all);
+    ``stats`` int64 [8], :data:`RESUME_STATS` in order.  Nothing is caught
+    up when ``bad[0] != 0``, for a segment with state :data:`SEG_EXPIRED` or
+    outside the table, for a watcher slot outside 0..63, or for a frame that
+    is not a well-formed SET_WATCHES.  No host read."""
+    lib().watch_resume_sessions(tree, rx, frame_off, frame_len, count,
+                                int(ncap), f_seg, wslots, seg_state, bad, ws,
+                                list(ev), ev_total, list(grouped), slot_first,
+                                stats)
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
