@@ -518,6 +518,28 @@ int zk_watch_resume_sessions(const ZkTree*, const uint8_t*, int64_t,
                              int64_t*, int64_t, int32_t*, int32_t*, int64_t*,
                              int32_t*, int64_t*, int32_t*, int32_t*, int64_t*,
                              int32_t*, int64_t*, int64_t*, hipStream_t);
+// Close / expire many sessions in one pass (tree_close.hip; the rules:
+// zk_close.h).  zk_close_workspace: int64 words for (frames a batch, sessions
+// a list, the tree's node slots); its head is the fired watches' record area
+// (zk_tree_expire's rec, cap_frames records).  zk_close_frames, between a
+// session batch's serve and its reply encode: (tree, rx, its length, frames
+// off / len, count, ncap, f_seg, sessions, wslots, seg_state, bad, S, the
+// serve's r_err, cap_frames, node slots, workspace) -> every CLOSE_SESSION
+// frame of a live segment answered OK, the closing segments' list and count
+// in the workspace, stats[8].  zk_close_sessions: (tree, sids[K], wslots[K]
+// or null, K, S, cap_frames, node slots, the session table or null, its
+// server id, workspace) -> removed[S] (+= per listed session), stats[8];
+// sids null: the list zk_close_frames left.
+int64_t zk_close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap);
+int zk_close_frames(const ZkTree*, const uint8_t*, int64_t, const int64_t*,
+                    const int32_t*, const int64_t*, int64_t, const int32_t*,
+                    const int64_t*, const int32_t*, const int32_t*,
+                    const int64_t*, int64_t, int32_t*, int64_t, int64_t,
+                    int64_t*, int64_t*, hipStream_t);
+int zk_close_sessions(const ZkTree*, const int64_t*, const int32_t*, int64_t,
+                      int64_t, int64_t, int64_t, const ZkSessionTable*,
+                      int64_t, int64_t*, unsigned long long*, int64_t*,
+                      hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

@@ -509,8 +509,15 @@ ZK_DEV int64_t ht_reclaim(const ZkTree& t, int64_t s, bool succ_empty = false);
 // every other live entry has no eraser in the launch, and its val is
 // claimed (-3: no lookup matches it) while it moves, so one thread moves it
 // and it is found at one slot or the other by any later launch.
-ZK_DEV void ht_shift(const ZkTree& t, int64_t s, int64_t session,
-                     int64_t tag) {
+//
+// ht_shift_if is the shift with "this live entry has no eraser in the launch"
+// as a functor over the entry's node (one load on the removal's dependent
+// path, whatever decides it); ht_shift below is the one-session form.  The
+// many-session close (tree_close.hip) marks the closing sessions' nodes in an
+// array before its removal launch and asks that.
+template <class Movable>
+ZK_DEV void ht_shift_if(const ZkTree& t, int64_t s, int64_t tag,
+                        Movable movable) {
   for (int moves = 0; moves < 16; ++moves) {
     // the first entry after the hole whose chain covers it: movable (any
     // live entry but `session`'s), or blocking (`session`'s, one moving or
@@ -552,7 +559,7 @@ ZK_DEV void ht_shift(const ZkTree& t, int64_t s, int64_t session,
       if (val > 0 &&
           ((j - (key & t.mask)) & t.mask) < ((j - s) & t.mask))
         continue;                                   // home after the hole
-      if (val > 0 && t.eph[val_node(val)] != session) {
+      if (val > 0 && movable(val_node(val))) {
         cand = j;
         cv = val;
       }
@@ -599,6 +606,12 @@ ZK_DEV void ht_shift(const ZkTree& t, int64_t s, int64_t session,
     s = cand;                                       // the new hole
   }
   ht_reclaim(t, s);
+}
+
+ZK_DEV void ht_shift(const ZkTree& t, int64_t s, int64_t session,
+                     int64_t tag) {
+  ht_shift_if(t, s, tag,
+              [&](int64_t node) { return t.eph[node] != session; });
 }
 
 ZK_DEV int64_t ht_reclaim(const ZkTree& t, int64_t s, bool succ_empty) {

@@ -1894,6 +1894,102 @@ void session_install(const std::vector<Tensor>& tab, const Tensor& rec,
          "session_install");
 }
 
+// Close / expire many sessions in one pass (tree_close.hip): int64 words of
+// the workspace for cap_frames frames a batch, lists of up to S sessions and
+// node_cap node slots.
+int64_t close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap) {
+  TORCH_CHECK(cap_frames >= 0 && S >= 1 && S < (1ll << 31) - 1 &&
+                  node_cap >= 0,
+              "zkmi: close_workspace cap_frames >= 0, 1 <= S < 2^31, "
+              "node_cap >= 0");
+  return zk_close_workspace(cap_frames, S, node_cap);
+}
+
+// Pass 1 of a session batch served with close: the CLOSE_SESSION frames of
+// the frame table -> r_err (OK), the closing segments' list in ws, stats.
+void close_frames(const std::vector<Tensor>& t, const Tensor& rx,
+                  const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
+                  int64_t ncap, const Tensor& f_seg, const Tensor& sessions,
+                  const Tensor& wslots, const Tensor& seg_state,
+                  const Tensor& bad, const Tensor& r_err, int64_t cap_frames,
+                  const Tensor& ws, const Tensor& stats) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  const int64_t S = sessions.numel();
+  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: close_frames ncap");
+  TORCH_CHECK(cap_frames >= 0, "zkmi: close_frames cap_frames");
+  hip_ok(zk_close_frames(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
+             P<int64_t>(sessions, I64, S, "sessions", d),
+             P<int32_t>(wslots, I32, S, "wslots", d),
+             P<int32_t>(seg_state, I32, S, "seg_state", d),
+             P<int64_t>(bad, I64, 2, "bad", d), S,
+             P<int32_t>(r_err, I32, ncap, "r_err", d), cap_frames,
+             s.store.cap,
+             P<int64_t>(ws, I64,
+                        zk_close_workspace(cap_frames, S, s.store.cap),
+                        "workspace", d),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "close_frames");
+}
+
+// Passes 2-7.  sids given: the direct form, K = its length (wslots, when
+// given, as long); else the list close_frames left in ws.  S: the sessions
+// the workspace was sized for (K <= S; removed has room for S).
+void close_sessions(const std::vector<Tensor>& t,
+                    const c10::optional<Tensor>& sids,
+                    const c10::optional<Tensor>& wslots, int64_t S,
+                    int64_t cap_frames, const std::vector<Tensor>& table,
+                    int64_t server_id, int64_t span, const Tensor& ws,
+                    const Tensor& removed, const Tensor& stats) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1, "zkmi: close_sessions S");
+  TORCH_CHECK(cap_frames >= 0, "zkmi: close_sessions cap_frames");
+  const bool direct = sids.has_value() && sids->defined();
+  int64_t K = 0;
+  const int64_t* sp = nullptr;
+  const int32_t* wp = nullptr;
+  if (direct) {
+    K = sids->numel();
+    TORCH_CHECK(K <= S, "zkmi: close_sessions lists ", K,
+                " sessions, the workspace holds ", S);
+    sp = P<int64_t>(*sids, I64, K, "sids", d);
+    if (wslots.has_value() && wslots->defined()) {
+      TORCH_CHECK(wslots->numel() == K, "zkmi: wslots has ", wslots->numel(),
+                  " entries, needs ", K);
+      wp = P<int32_t>(*wslots, I32, K, "wslots", d);
+    }
+  } else {
+    TORCH_CHECK(!wslots.has_value() || !wslots->defined(),
+                "zkmi: close_sessions wslots without sids");
+  }
+  ZkSessionTable tab{};
+  const bool has_tab = !table.empty();
+  if (has_tab) {
+    tab = session_table(table, span);
+    TORCH_CHECK(table[0].device() == d->device(),
+                "zkmi: session table on the tree's device");
+    TORCH_CHECK(server_id >= 0 && server_id < 128, "zkmi: server_id");
+  }
+  hip_ok(zk_close_sessions(
+             &s, sp, wp, K, S, cap_frames, s.store.cap,
+             has_tab ? &tab : nullptr, server_id,
+             P<int64_t>(ws, I64,
+                        zk_close_workspace(cap_frames, S, s.store.cap),
+                        "workspace", d),
+             reinterpret_cast<unsigned long long*>(
+                 P<int64_t>(removed, I64, direct ? K : S, "removed", d)),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "close_sessions");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(zkmi, m) {
@@ -2154,4 +2250,15 @@ TORCH_LIBRARY(zkmi, m) {
         "int span=0) -> ()", &session_close);
   m.def("session_install(Tensor(a!)[] table, Tensor records, int server_id, "
         "int span) -> ()", &session_install);
+  m.def("close_workspace(int cap_frames, int S, int node_cap) -> int",
+        &close_workspace);
+  m.def("close_frames(Tensor[] tree, Tensor rx, Tensor frame_off, "
+        "Tensor frame_len, Tensor count, int ncap, Tensor f_seg, "
+        "Tensor sessions, Tensor wslots, Tensor seg_state, Tensor bad, "
+        "Tensor(a!) r_err, int cap_frames, Tensor(b!) ws, Tensor(c!) stats) "
+        "-> ()", &close_frames);
+  m.def("close_sessions(Tensor(a!)[] tree, Tensor? sids, Tensor? wslots, "
+        "int S, int cap_frames, Tensor(b!)[] table, int server_id, int span, "
+        "Tensor(c!) ws, Tensor(d!) removed, Tensor(e!) stats) -> ()",
+        &close_sessions);
 }

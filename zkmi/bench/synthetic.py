@@ -723,6 +723,9 @@ class GpuServer(object):
         self.resume_notif = None          # the last SET_WATCHES catch-up
         self.resume_slots = None          # (slot_first, slot_off) of a
         self._rs = None                   # session batch's (buffers: lazy)
+        self.close_notif = None           # what the last close pass fired
+        self.close_slots = None           # (slot_first, slot_off) of it
+        self._cl = None                   # (buffers: lazy)
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -1109,7 +1112,8 @@ class GpuServer(object):
         return st
 
     def serve_sessions(self, rx, n, segs, ordered=False, passes=4,
-                       terminate=False, table=None, resume=False):
+                       terminate=False, table=None, resume=False,
+                       close=False):
         """Serve ``rx[:n]``, the concatenated whole frames of the
         ``segs.S`` connections of :class:`SessionSegments` ``segs``, as ONE
         batch: one K1 scan and one serve (``passes`` of them when
@@ -1186,7 +1190,36 @@ class GpuServer(object):
         and :meth:`resume_stats` reads its counters.  Its buffers are sized
         from ``rx.numel()``, allocated on first use and grown when a larger
         ``rx`` comes; a call that does not grow them is capturable where the
-        call without ``resume`` is."""
+        call without ``resume`` is.
+
+        ``close``: serve the batch's CLOSE_SESSION frames
+        (csrc/kernels/tree_close.hip; the rules: zk_close.h).  Off, such a
+        frame is answered UNIMPLEMENTED and nothing else.  On, a
+        CLOSE_SESSION frame of a live segment of a sound table is answered OK
+        (the same 20 bytes, its own xid) and closes its segment: the
+        segment's session and watcher slot join the list of one
+        :meth:`close_sessions` pass that runs after the serve, and after the
+        ``resume`` catch-up when both are set — as if every CLOSE_SESSION
+        frame of the batch came after all its other frames, in segment order
+        among themselves (the k-th closing segment's removals carry zxid
+        base + k + 1, base the counter after the batch's own zxids).  So
+        frames of a segment after its CLOSE_SESSION are served (the
+        reference client sends it only when nothing is outstanding);
+        ephemerals the closing connection creates in the same batch go with
+        it, while another connection's read in that batch still sees them;
+        the batch's write-fired notifications addressed to a closing watcher
+        stay in ``self.notif``, but nothing of the close pass is addressed
+        to one, and what the catch-up re-armed for it is dropped.  A refused
+        frame closes nothing: an unsound table (SYSTEMERROR), a segment
+        whose session is not alive (SESSION_EXPIRED), a body shorter than 8
+        bytes (BAD_ARGUMENTS).  With ``table`` the closed sessions' entries
+        die: their next batch is answered SESSION_EXPIRED.  It leaves
+        ``self.close_notif`` / ``self.close_slots`` as
+        :meth:`close_sessions` does (a front end writes a watcher's
+        ``resume_notif`` slice, then its ``notif`` slice, then its
+        ``close_notif`` slice), ``self.close_removed`` (int64 [S]: nodes
+        removed for the k-th closing segment) and the counters of
+        :meth:`close_stats`; nothing is read back."""
         L = _lib.lib()
         if self.fused_rows or self.read_only:
             raise ValueError('serve_sessions: no session form of the '
@@ -1235,6 +1268,8 @@ class GpuServer(object):
             _lib.tree_acl_record(tree.acl, rx, ft.off, ft.length, ft.count,
                                  self.cap_frames, r.opcode, r.err, r.node,
                                  self._acl_workspace())
+        if close:
+            self._close_frames(rx, ft, sg.f_seg, segs)
         out, rec_off, total, err = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
@@ -1255,6 +1290,8 @@ class GpuServer(object):
         else:
             _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
                              total, err, sg.rep_off)
+        if close:
+            self._close_batch(segs, table)
         return self.result
 
     def session_stats(self):
@@ -1269,6 +1306,174 @@ class GpuServer(object):
         v = torch.cat([sg.bad, (sg.state == 1).sum().view(1)]).cpu().tolist()
         return {'bad': v[0], 'first_bad_segment': v[1],
                 'expired_segments': v[2]}
+
+    # -- closing many sessions ------------------------------------------------
+
+    def _close_buffers(self, S):
+        """The close passes' buffers for lists of up to ``S`` sessions
+        (csrc/kernels/tree_close.hip), allocated on first use and grown when
+        a longer list comes; on a tree with a watch table also those of the
+        events the removals fire, apart from the batch's own (``self.notif``
+        keeps what the batch's writes fired)."""
+        tree = self.tree
+        dev = tree.device
+        cap = self.cap_frames
+        need = _lib.close_workspace(cap, S, tree.cap)
+        b = self._cl
+        if b is None:
+            b = {'ws': None, 'stats': torch.zeros(8, dtype=I64, device=dev),
+                 'removed': None}
+            if tree.watch is not None:
+                ecap = self.ecap
+                rec = lambda: [torch.zeros(ecap, dtype=I32, device=dev),
+                               torch.zeros(ecap, dtype=I32, device=dev),
+                               torch.zeros(ecap, dtype=I64, device=dev),
+                               torch.zeros(ecap, dtype=I32, device=dev)]
+                b.update({
+                    'ev': rec(), 'g': rec(),
+                    'ev_total': torch.zeros(2, dtype=I64, device=dev),
+                    'group_ws': torch.empty(_lib.sess_group_workspace(ecap),
+                                            dtype=I64, device=dev),
+                    'first': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                         device=dev),
+                    'off': torch.zeros(_lib.SESS_SLOTS + 1, dtype=I64,
+                                       device=dev),
+                    'total_err': B._total_err(dev),
+                    'rec_off': torch.zeros(ecap, dtype=I64, device=dev),
+                    'buf': torch.empty(self.notif_buf.numel(), dtype=U8,
+                                       device=dev),
+                    # every record is a removal: a DELETE that succeeded
+                    'op': torch.full((cap,), consts.OP_CODES['DELETE'],
+                                     dtype=I32, device=dev),
+                    'err': torch.zeros(cap, dtype=I32, device=dev),
+                    # sess_ranges' reply half: one segment without a frame
+                    'nil': (torch.zeros(2, dtype=I64, device=dev),
+                            torch.zeros(1, dtype=I64, device=dev),
+                            torch.zeros(1, dtype=I32, device=dev),
+                            torch.zeros(2, dtype=I64, device=dev))})
+                g = b['g']
+                b['resp'] = self._notif_batch(g[2], g[3], tree.path_arena,
+                                              g[1], b['ev_total'][0:1], ecap,
+                                              dev)
+            self._cl = b
+        if b['ws'] is None or b['ws'].numel() < need:
+            b['ws'] = torch.empty(need, dtype=I64, device=dev)
+        if b['removed'] is None or b['removed'].numel() < S:
+            b['removed'] = torch.zeros(S, dtype=I64, device=dev)
+        return b
+
+    def _close_frames(self, rx, frames, f_seg, segs):
+        """Pass 1 of a session batch served with ``close``: between the serve
+        of ``frames`` and the encode of its replies."""
+        b = self._close_buffers(segs.S)
+        sg = self.seg
+        _lib.close_frames(self.tree.tensors, rx, frames.off, frames.length,
+                          frames.count, self.cap_frames, f_seg, segs.sessions,
+                          segs.wslots, sg.state, sg.bad, self.resp.err,
+                          self.cap_frames, b['ws'], b['stats'])
+
+    def _close_batch(self, segs, table):
+        """Passes 2-7 of a session batch served with ``close``, over the list
+        :meth:`_close_frames` left on the device."""
+        b = self._close_buffers(segs.S)
+        self.close_removed = b['removed'][:segs.S]
+        self.close_removed.zero_()
+        self._close_pass(segs.S, None, None, table, self.close_removed)
+
+    def _close_pass(self, S, sids, wslots, table, removed):
+        """Passes 2-7 and, on a tree with a watch table, the events: the
+        records of the removals' fired watches expanded, grouped by watcher
+        slot and encoded, as :meth:`_notify_grouped` does a batch's."""
+        tree = self.tree
+        b = self._close_buffers(S)
+        cap = self.cap_frames
+        _lib.close_sessions(
+            tree.tensors, sids, wslots, S, cap, b['ws'], removed, b['stats'],
+            table=None if table is None else table._tensors,
+            server_id=0 if table is None else table.server_id,
+            span=0 if table is None else table.span)
+        if tree.watch is None:
+            return
+        rec = b['ws'][:8 + 5 * cap]
+        ev, g = b['ev'], b['g']
+        _lib.lib().watch_events(b['op'], b['err'], rec[0:1], cap, rec[8:],
+                                self.wbsum, ev[0], ev[1], ev[2], ev[3],
+                                b['ev_total'])
+        _lib.sess_group_events(ev[0], ev[1], ev[2], ev[3], b['ev_total'],
+                               b['group_ws'], g[0], g[1], g[2], g[3],
+                               b['first'])
+        out, _, total, _ = B.encode_responses(
+            b['resp'], tree.store, b['buf'].numel(), out=b['buf'],
+            total_err=b['total_err'], rec_off=b['rec_off'])
+        nil = b['nil']
+        _lib.sess_ranges(nil[0], nil[1], nil[1], 1, nil[1], nil[2], nil[3],
+                         b['first'], b['rec_off'], b['ev_total'][0:1],
+                         b['total_err'][0], b['total_err'][1], b['off'])
+        self.close_notif = (out, total, g[0], b['ev_total'][0:1])
+        self.close_slots = (b['first'], b['off'])
+
+    def close_sessions(self, sids, wslots=None, table=None, removed=None):
+        """End the sessions ``sids`` (device int64 [K]) in ONE pass
+        (csrc/kernels/tree_close.hip; the rules: zk_close.h): the sessions a
+        front end's timer expired, or that it closes for reasons of its own.
+        What K calls of :meth:`expire` (and one of
+        :meth:`GpuSessionTable.close`) do with K sweeps of the node table
+        and of the watch table, in one sweep of each; no host read.
+
+        Session ``sids[k]``'s ephemerals are removed as its own closeSession
+        txn, zxid base + k + 1, and the zxid counter moves by K: the tree is
+        the one ``expire(sids[0]) ... expire(sids[K - 1])`` leaves.  An id
+        listed twice removes at its first position, id 0 and an id that owns
+        nothing remove nothing; each still takes its zxid.  Returns
+        ``removed`` (device int64 [K], accumulated): the nodes removed for
+        each listed session.
+
+        ``wslots`` (device int32 [K]): the sessions' watcher slots.  On a
+        tree with a watch table their bits are dropped from every mask
+        before anything is removed (a value outside 0..63 drops nothing), so
+        a closing session is told nothing and the next session bound to its
+        slot inherits nothing; the watches the removals fire for the others
+        are left in
+
+        ``self.close_notif``  ``(buf, total, slots, count)``: the xid -1
+                              frames grouped by watcher slot, in no defined
+                              order inside a slot (as :meth:`expire`'s);
+        ``self.close_slots``  ``(slot_first, slot_off)``, both [65]: watcher
+                              w's are ``buf[slot_off[w]:slot_off[w + 1]]``.
+
+        Room for ``cap_frames`` removals that fire a watch; more are counted
+        by :meth:`close_stats` and their events lost.  ``table``: a
+        :class:`GpuSessionTable`; the listed ids' entries close (an id it
+        does not hold touches nothing)."""
+        K = int(sids.numel())
+        dev = self.tree.device
+        if removed is None:
+            removed = torch.zeros(K, dtype=I64, device=dev)
+        if K == 0:
+            return removed
+        self._close_pass(K, sids, wslots, table, removed)
+        return removed
+
+    def close_stats(self):
+        """Of the last close pass (:meth:`close_sessions`, or a session batch
+        served with ``close=True``), one host read: ``frames`` (closing
+        CLOSE_SESSION frames; 0 for the direct form), ``sessions`` (K),
+        ``removed`` (nodes, all sessions), ``events_fired`` /
+        ``events_written`` (fewer written: the event room overflowed),
+        ``records_dropped`` (removals whose fired watches found no record:
+        past ``cap_frames``) and ``encode_err`` (the events' encoder's flag;
+        2: the notification buffer is too small)."""
+        b = self._cl
+        if b is None:
+            raise ValueError('close_stats: no close pass has run')
+        parts = [b['stats'][:3]]
+        if self.tree.watch is not None:
+            parts += [b['ev_total'], b['ws'][0:1],
+                      b['total_err'][1].to(I64)]
+        v = torch.cat(parts).cpu().tolist() + [0, 0, 0, 0]
+        return dict(zip(_lib.CLOSE_STATS,
+                        [v[0], v[1], v[2], v[4], v[3],
+                         max(0, v[5] - self.cap_frames), v[6]]))
 
     def serve_list(self, rx, n, wslot=-1, terminate=False, max_frame=None,
                    out=None):
@@ -1507,7 +1712,8 @@ class GpuServer(object):
         return self.result
 
     def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
-                             max_frame=None, out=None, resume=False):
+                             max_frame=None, out=None, resume=False,
+                             close=False):
         """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
         connections of :class:`SessionSegments` ``segs``, whatever ops they
         mix, as ONE batch: :meth:`serve_sessions` for every op of
@@ -1562,6 +1768,13 @@ class GpuServer(object):
         never hits the re-armed watch, and a ``watch=1`` list of the batch is
         armed before it.  Off, a SET_WATCHES frame gets its header-only
         reply and nothing else; on, the replies are the same.
+
+        ``close``: the batch's CLOSE_SESSION frames are served, as in
+        :meth:`serve_sessions` (``self.close_notif``, ``self.close_slots``,
+        ``self.close_removed``, :meth:`close_stats`).  The frame is of the
+        serve's class; the close pass runs once, after the three engines and
+        after the ``resume`` catch-up, so a list or a GET_ACL of the batch
+        still sees a closing connection's ephemerals.
 
         Not offered: in-batch ordering (``serve_sessions(ordered=True)``).
 
@@ -1622,6 +1835,8 @@ class GpuServer(object):
             _lib.tree_acl_record(tree.acl, rx, fa.off, fa.length, fa.count,
                                  cap, r.opcode, r.err, r.node,
                                  self._acl_workspace())
+        if close:
+            self._close_frames(rx, fa, seg_c[0], segs)
         a_out, _, a_total, a_err = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=False,
@@ -1668,6 +1883,8 @@ class GpuServer(object):
         else:
             _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
                              sg.rep_off)
+        if close:
+            self._close_batch(segs, table)
         return self.result
 
     def acl_stats(self):

@@ -407,5 +407,56 @@ def watch_resume_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
                                 stats)
 
 
+# close / expire many sessions in one pass (csrc/kernels/tree_close.hip; the
+# rules: zk_close.h).  What GpuServer.close_stats reports, in order: the
+# first three are the passes' own counters (stats[0..2])
+CLOSE_STATS = ('frames', 'sessions', 'removed', 'events_fired',
+               'events_written', 'records_dropped', 'encode_err')
+
+
+def close_workspace(cap_frames, S, node_cap):
+    """int64 words of the close passes' workspace for a server of
+    ``cap_frames`` frames a batch, lists of up to ``S`` sessions and a tree of
+    ``node_cap`` node slots (nothing in it needs zeroing).  Its first ``8 + 5
+    * cap_frames`` words are the record area of the watches the removals
+    fire, laid out as :meth:`GpuTree.expire`'s ``rec``."""
+    return lib().close_workspace(int(cap_frames), int(S), int(node_cap))
+
+
+def close_frames(tree, rx, frame_off, frame_len, count, ncap, f_seg,
+                 sessions, wslots, seg_state, bad, r_err, cap_frames, ws,
+                 stats):
+    """Between a session batch's serve and its reply encode, on the current
+    stream: every CLOSE_SESSION frame of a live segment of a sound table
+    (``bad[0] == 0``, state :data:`SEG_SERVE`, a body of 8 bytes or more)
+    whose reply the serve left UNIMPLEMENTED is answered OK in ``r_err`` and
+    closes its segment.  The closing segments' sessions and watcher slots,
+    in segment order, and their number stay in ``ws`` for
+    :func:`close_sessions` without ``sids``.  ``stats`` (int64 [8]) is
+    zeroed; ``stats[0]`` counts the closing frames.  No host read."""
+    lib().close_frames(tree, rx, frame_off, frame_len, count, int(ncap),
+                       f_seg, sessions, wslots, seg_state, bad, r_err,
+                       int(cap_frames), ws, stats)
+
+
+def close_sessions(tree, sids, wslots, S, cap_frames, ws, removed, stats,
+                   table=None, server_id=0, span=0):
+    """End the listed sessions in one pass, on the current stream: ``sids``
+    (int64 [K], K <= ``S``) with ``wslots`` (int32 [K] or None), or, with
+    ``sids`` None, the list :func:`close_frames` left in ``ws``.  The
+    ephemerals of session rank k go with zxid base + k + 1 and are counted
+    in ``removed[k]`` (accumulated; int64 [K], [S] without ``sids``); the
+    zxid counter moves by K.  On a tree with a watch table the listed
+    watcher slots' bits are dropped from every mask first, and the watches
+    the removals fire are recorded in the head of ``ws``.  ``table``: a
+    session table's tensors, whose entries of the listed ids close.
+    ``stats`` (int64 [8]): ``[1]`` K, ``[2]`` nodes removed.  ``ws``:
+    :func:`close_workspace` of (``cap_frames``, ``S``, the tree's node
+    slots).  No host read."""
+    lib().close_sessions(tree, sids, wslots, int(S), int(cap_frames),
+                         list(table or []), int(server_id), int(span), ws,
+                         removed, stats)
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
