@@ -540,6 +540,24 @@ int zk_close_sessions(const ZkTree*, const int64_t*, const int32_t*, int64_t,
                       int64_t, int64_t, int64_t, const ZkSessionTable*,
                       int64_t, int64_t*, unsigned long long*, int64_t*,
                       hipStream_t);
+// The front end's I/O staging (front.hip; the rules: zk_front.h).
+// zk_front_chunk: bytes of the cut's staged window.  zk_front_cut: (raw, n,
+// raw_starts[S + 1], S, quota, max_packet) -> take[S], nfr[S], flag[S],
+// fault[1].  zk_front_gather: (streams[4] and caps[4] on the host, p_stream[P]
+// or null, p_src[P], the scanned p_off[P + 1], P, dst, its capacity) -> the
+// pieces packed into dst, over[1].  zk_front_tx_pieces: (rep_off[S + 1] or
+// null, wslots[S], slot_off[3] on the host — each [65] or null —, the batch's
+// err or null, caps[4] on the host, S, owner[64]) -> p_stream / p_src / p_len
+// [4 S], stats[8].
+int64_t zk_front_chunk(void);
+int zk_front_cut(const uint8_t*, int64_t, const int64_t*, int64_t, int64_t,
+                 int64_t, int64_t*, int32_t*, int32_t*, int64_t*, hipStream_t);
+int zk_front_gather(const uint8_t* const*, const int64_t*, const int32_t*,
+                    const int64_t*, const int64_t*, int64_t, uint8_t*, int64_t,
+                    int64_t*, hipStream_t);
+int zk_front_tx_pieces(const int64_t*, const int32_t*, const int64_t* const*,
+                       const int32_t*, const int64_t*, int64_t, int64_t*,
+                       int32_t*, int64_t*, int64_t*, int64_t*, hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

@@ -1990,6 +1990,87 @@ void close_sessions(const std::vector<Tensor>& t,
          "close_sessions");
 }
 
+// The front end's I/O staging (front.hip).
+int64_t front_chunk() { return zk_front_chunk(); }
+
+// The cut: raw[:n] with raw_starts [S + 1] -> take / nfr / flag [S], fault.
+void front_cut(const Tensor& raw, int64_t n, const Tensor& raw_starts,
+               int64_t quota, int64_t max_packet, const Tensor& take,
+               const Tensor& nfr, const Tensor& flag, const Tensor& fault) {
+  const Tensor* d = &raw;
+  const int64_t S = raw_starts.numel() - 1;
+  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(n >= 0 && n <= raw.numel(), "zkmi: front_cut n is ", n,
+              ", raw holds ", raw.numel());
+  TORCH_CHECK(max_packet >= 0 && max_packet < (1ll << 31),
+              "zkmi: front_cut max_packet");
+  hip_ok(zk_front_cut(P<uint8_t>(raw, U8, std::max<int64_t>(n, 1), "raw"), n,
+                      P<int64_t>(raw_starts, I64, S + 1, "raw_starts", d), S,
+                      quota, max_packet, P<int64_t>(take, I64, S, "take", d),
+                      P<int32_t>(nfr, I32, S, "nfr", d),
+                      P<int32_t>(flag, I32, S, "flag", d),
+                      P<int64_t>(fault, I64, 1, "fault", d), cur_stream()),
+         "front_cut");
+}
+
+// The gather: piece i of P (p_off [P + 1] scanned) from streams[p_stream[i]]
+// (stream 0 without p_stream) into dst.  A stream of no elements is absent.
+void front_gather(const std::vector<Tensor>& streams,
+                  const c10::optional<Tensor>& p_stream, const Tensor& p_src,
+                  const Tensor& p_off, int64_t np, const Tensor& dst,
+                  const Tensor& over) {
+  TORCH_CHECK(streams.size() >= 1 && streams.size() <= 4,
+              "zkmi: front_gather takes 1 to 4 streams, got ", streams.size());
+  TORCH_CHECK(np >= 1 && np < (1ll << 31) - 1, "zkmi: front_gather pieces");
+  const Tensor* d = &dst;
+  const uint8_t* sp[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t caps[4] = {0, 0, 0, 0};
+  for (size_t k = 0; k < streams.size(); ++k) {
+    if (streams[k].numel() == 0) continue;
+    sp[k] = P<uint8_t>(streams[k], U8, 1, "stream", d);
+    caps[k] = streams[k].numel();
+  }
+  hip_ok(zk_front_gather(sp, caps,
+                         Popt<int32_t>(p_stream, I32, np, "p_stream", d),
+                         P<int64_t>(p_src, I64, np, "p_src", d),
+                         P<int64_t>(p_off, I64, np + 1, "p_off", d), np,
+                         P<uint8_t>(dst, U8, 0, "dst"), dst.numel(),
+                         P<int64_t>(over, I64, 1, "over", d), cur_stream()),
+         "front_gather");
+}
+
+// The TX pieces of S connections: 4 S descriptors, in sending order.
+void front_tx_pieces(const c10::optional<Tensor>& rep_off,
+                     const Tensor& wslots,
+                     const c10::optional<Tensor>& resume_off,
+                     const c10::optional<Tensor>& notif_off,
+                     const c10::optional<Tensor>& close_off,
+                     const c10::optional<Tensor>& err,
+                     std::vector<int64_t> caps, const Tensor& owner,
+                     const Tensor& p_stream, const Tensor& p_src,
+                     const Tensor& p_len, const Tensor& stats) {
+  const Tensor* d = &wslots;
+  const int64_t S = wslots.numel();
+  TORCH_CHECK(S >= 1 && S < (1ll << 29),
+              "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(caps.size() == 4, "zkmi: front_tx_pieces takes 4 capacities");
+  const int64_t* so[3] = {
+      Popt<int64_t>(resume_off, I64, 65, "resume_off", d),
+      Popt<int64_t>(notif_off, I64, 65, "notif_off", d),
+      Popt<int64_t>(close_off, I64, 65, "close_off", d)};
+  hip_ok(zk_front_tx_pieces(
+             Popt<int64_t>(rep_off, I64, S + 1, "rep_off", d),
+             P<int32_t>(wslots, I32, S, "wslots"), so,
+             Popt<int32_t>(err, I32, 1, "err", d), caps.data(), S,
+             P<int64_t>(owner, I64, 64, "owner", d),
+             P<int32_t>(p_stream, I32, 4 * S, "p_stream", d),
+             P<int64_t>(p_src, I64, 4 * S, "p_src", d),
+             P<int64_t>(p_len, I64, 4 * S, "p_len", d),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "front_tx_pieces");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(zkmi, m) {
@@ -2261,4 +2342,15 @@ TORCH_LIBRARY(zkmi, m) {
         "int S, int cap_frames, Tensor(b!)[] table, int server_id, int span, "
         "Tensor(c!) ws, Tensor(d!) removed, Tensor(e!) stats) -> ()",
         &close_sessions);
+  m.def("front_chunk() -> int", &front_chunk);
+  m.def("front_cut(Tensor raw, int n, Tensor raw_starts, int quota, "
+        "int max_packet, Tensor(a!) take, Tensor(b!) nfr, Tensor(c!) flag, "
+        "Tensor(d!) fault) -> ()", &front_cut);
+  m.def("front_gather(Tensor[] streams, Tensor? p_stream, Tensor p_src, "
+        "Tensor p_off, int P, Tensor(a!) dst, Tensor(b!) over) -> ()",
+        &front_gather);
+  m.def("front_tx_pieces(Tensor? rep_off, Tensor wslots, Tensor? resume_off, "
+        "Tensor? notif_off, Tensor? close_off, Tensor? err, int[] caps, "
+        "Tensor(a!) owner, Tensor(b!) p_stream, Tensor(c!) p_src, "
+        "Tensor(d!) p_len, Tensor(e!) stats) -> ()", &front_tx_pieces);
 }

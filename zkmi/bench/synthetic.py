@@ -1111,6 +1111,14 @@ class GpuServer(object):
         st['encode_err'] = v[-1]
         return st
 
+    def resume_counters(self):
+        """The device counters :meth:`resume_stats` reads (int64 [8], in
+        ``_lib.RESUME_STATS`` order), for a caller that folds them into a
+        read of its own (the front end's report); no host read."""
+        if self._rs is None:
+            raise ValueError('resume_counters: no session batch was resumed')
+        return self._rs['stats']
+
     def serve_sessions(self, rx, n, segs, ordered=False, passes=4,
                        terminate=False, table=None, resume=False,
                        close=False):

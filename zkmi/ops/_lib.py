@@ -458,5 +458,69 @@ def close_sessions(tree, sids, wslots, S, cap_frames, ws, removed, stats,
                          removed, stats)
 
 
+# the front end's TX streams, in the order a connection's pieces are sent
+# (csrc/kernels/zk_front.h FS_*), and its assembly counters (FTS_*)
+FS_REPLY, FS_RESUME, FS_NOTIF, FS_CLOSE = range(4)
+FRONT_PIECES = 4
+FRONT_STATS = ('dup_slot',)
+
+
+def front_chunk():
+    """Bytes of :func:`front_cut`'s staged window (csrc/kernels/front.hip
+    FC_CHUNK): a word of a segment that straddles a multiple of it is read
+    from a window of its own."""
+    return lib().front_chunk()
+
+
+def front_cut(raw, n, raw_starts, quota, max_packet, take, nfr, flag, fault):
+    """The front end's cut (csrc/kernels/front.hip; the rule: zk_front.h
+    front_walk), on the current stream: what every connection has received,
+    ``raw[:n]`` with ``raw_starts`` (int64 [S + 1]; segment s is
+    ``raw[raw_starts[s]:raw_starts[s + 1]]``, partial trailing frames
+    included), cut at a frame boundary.  ``take`` (int64 [S]): the bytes of
+    each segment to serve now — whole frames only, at most ``quota`` of them,
+    any number of non-write frames or exactly one write frame (CREATE,
+    DELETE, SET_DATA, CLOSE_SESSION); ``nfr`` (int32 [S]): the frames in
+    them; ``flag`` (int32 [S]): 1 where the walk met a length < 0 or >
+    ``max_packet`` (nothing at or after it is taken).  ``fault`` (int64
+    [1]): 1 when ``raw_starts`` does not begin at 0, descends or passes
+    ``n``; then nothing is taken anywhere.  No host read."""
+    lib().front_cut(raw, int(n), raw_starts, int(quota), int(max_packet),
+                    take, nfr, flag, fault)
+
+
+def front_gather(streams, p_stream, p_src, p_off, P, dst, over):
+    """Pack ``P`` pieces into ``dst`` (csrc/kernels/front.hip
+    front_gather_k), on the current stream: piece i is ``p_off[i + 1] -
+    p_off[i]`` bytes at ``p_src[i]`` of ``streams[p_stream[i]]`` (1 to 4
+    uint8 tensors, one of no elements is absent; ``p_stream`` None: all of
+    stream 0) and goes to ``dst[p_off[i]:p_off[i + 1]]``; ``p_off`` (int64
+    [P + 1]) is the exclusive scan of the lengths with the total behind.  A
+    piece that does not lie inside its stream is not copied.  ``over``
+    (int64 [1]): 1 when the total is past ``dst.numel()``; then nothing is
+    written.  No host read."""
+    lib().front_gather(list(streams), p_stream, p_src, p_off, int(P), dst,
+                       over)
+
+
+def front_tx_pieces(rep_off, wslots, resume_off, notif_off, close_off, err,
+                    caps, owner, p_stream, p_src, p_len, stats):
+    """The four pieces of every connection's bytes for its socket
+    (csrc/kernels/front.hip; the rule: zk_front.h front_piece), on the
+    current stream, in sending order: its replies ``rep_off[s]:rep_off[s +
+    1]`` of stream 0, then watcher slot ``wslots[s]``'s slices of the
+    catch-up, write-fired and close-fired notification streams (``*_off``:
+    int64 [65]).  A slot's slices go to the lowest-numbered segment naming
+    it; a second one gets none and is counted in ``stats[0]`` (int64 [8]).
+    A ``wslots`` value outside 0..63 gets replies only, an absent table
+    (None) or a batch whose ``err`` (int32 [1] or None) is not 0 gives
+    empty pieces, and so does a slice outside ``caps`` (the four streams'
+    bytes).  ``owner``: int64 [64] workspace.  Piece 4 s + k -> ``p_stream``
+    (int32), ``p_src``, ``p_len`` (int64), each [4 S].  No host read."""
+    lib().front_tx_pieces(rep_off, wslots, resume_off, notif_off, close_off,
+                          err, [int(c) for c in caps], owner, p_stream, p_src,
+                          p_len, stats)
+
+
 def available():
     return os.path.exists(LIB_PATH) and os.path.exists(HIP_LIB_PATH)
