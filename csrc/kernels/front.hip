@@ -16,6 +16,9 @@
 //                   so a length or an opcode word that straddles a chunk is
 //                   read whole from the next one, and a long body is skipped,
 //                   not staged.  -> take[s], nfr[s], flag[s]
+//                   (front_cut_k<true>: front_walk_ordered, the cut in front of
+//                   the ordered session serve, and nwr[s]; the phase is one
+//                   more word of that state)
 //   (the device-wide scan of take[]: starts[S + 1] of the session batch)
 //   front_gather_k  the taken prefixes packed into the dense rx
 //
@@ -26,6 +29,8 @@
 //                   count of segments that name a slot another one owns
 //   front_pieces_k  a lane per connection: its four piece descriptors
 //                   (stream, offset, length), in sending order
+//                   (front_pieces_k<true>: the replies end at rep_end[s], the
+//                   ordered serve's deferral)
 //   (the device-wide scan of the lengths: tx_off and the total)
 //   front_gather_k  the same kernel: the pieces into one TX buffer
 //
@@ -73,12 +78,15 @@ ZK_DEV uint4 fc_fetch(const uint8_t* __restrict__ raw, int64_t p, int64_t end) {
   return v;
 }
 
+// ORD: front_walk_ordered (has_acl: zk_mix.h's class rule) and nwr[s], the
+// write frames taken; the plain instance reads neither.
+template <bool ORD>
 __global__ __launch_bounds__(FC_T) void front_cut_k(
     const uint8_t* __restrict__ raw, int64_t n, int64_t raw_mis,
     const int64_t* __restrict__ raw_starts, int64_t S, int64_t quota,
     int64_t max_packet, const int64_t* __restrict__ fault,
     int64_t* __restrict__ take, int32_t* __restrict__ nfr,
-    int32_t* __restrict__ flag) {
+    int32_t* __restrict__ flag, int32_t has_acl, int32_t* __restrict__ nwr) {
   // (one word past the window: the high half of the last word's pair)
   __shared__ __attribute__((aligned(16))) uint32_t win[FC_CHUNK / 4 + 4];
   const int lane = threadIdx.x;
@@ -94,6 +102,7 @@ __global__ __launch_bounds__(FC_T) void front_cut_k(
     if (b < a) b = a;
   }
   FrontCut c{0, 0, 0};
+  int32_t wr = 0;                        // (ORD)
   if (b - a >= 4) {                      // (else: the wave leaves at once)
     // everything of the walk is wave-uniform: the window's base included
     int64_t wb = -((int64_t)1 << 62);    // no window yet
@@ -118,12 +127,20 @@ __global__ __launch_bounds__(FC_T) void front_cut_k(
       return __builtin_amdgcn_readfirstlane(
           (int32_t)bswap32((uint32_t)(two >> (8 * (r & 3)))));
     };
-    c = front_walk(b - a, quota, max_packet, rd);
+    if (ORD) {
+      const FrontCutOrd o =
+          front_walk_ordered(b - a, quota, max_packet, has_acl != 0, rd);
+      c.take = o.take, c.nfr = o.nfr, c.flag = o.flag;
+      wr = o.nwr;
+    } else {
+      c = front_walk(b - a, quota, max_packet, rd);
+    }
   }
   if (lane == 0) {
     take[s] = c.take;
     nfr[s] = c.nfr;
     flag[s] = c.flag;
+    if (ORD) nwr[s] = wr;
   }
 }
 
@@ -235,6 +252,8 @@ __global__ __launch_bounds__(FG_T) void front_owner_k(
   if (t == 0) stats[FTS_DUP] = dup;
 }
 
+// END: t.rep_end ends the reply pieces; the plain instance does not read it.
+template <bool END>
 __global__ __launch_bounds__(FG_T) void front_pieces_k(
     FrontTx t, int32_t* __restrict__ p_stream, int64_t* __restrict__ p_src,
     int64_t* __restrict__ p_len) {
@@ -242,7 +261,7 @@ __global__ __launch_bounds__(FG_T) void front_pieces_k(
   if (s >= t.S) return;
 #pragma unroll
   for (int k = 0; k < FRONT_PIECES; ++k) {
-    const FrontPiece p = front_piece(t, s, k);
+    const FrontPiece p = front_piece<END>(t, s, k);
     p_stream[FRONT_PIECES * s + k] = p.stream;
     p_src[FRONT_PIECES * s + k] = p.src;
     p_len[FRONT_PIECES * s + k] = p.len;
@@ -268,20 +287,38 @@ int64_t zk_front_chunk(void) { return zk::FC_CHUNK; }
 // raw_starts[s + 1])), at most `quota` frames a segment, K1's max_packet ->
 // take[S] (bytes to serve), nfr[S] (frames in them), flag[S] (1: bad length)
 // and fault[1] (1: the table is unsound; then every take is 0).
-int zk_front_cut(const uint8_t* raw, int64_t n, const int64_t* raw_starts,
-                 int64_t S, int64_t quota, int64_t max_packet, int64_t* take,
-                 int32_t* nfr, int32_t* flag, int64_t* fault, hipStream_t st) {
-  if (S < 1 || S > 0x7fffffff || n < 0 || max_packet < 0)
+// mode 0: front_walk.  mode 1: front_walk_ordered, with has_acl (the tree
+// keeps an ACL table: GET_ACL is of the ACL engine's class) -> nwr[S] too, the
+// write frames taken (mode 0 takes nwr null and leaves it alone).
+int zk_front_cut_mode(const uint8_t* raw, int64_t n, const int64_t* raw_starts,
+                      int64_t S, int64_t quota, int64_t max_packet,
+                      int32_t mode, int32_t has_acl, int64_t* take,
+                      int32_t* nfr, int32_t* flag, int32_t* nwr,
+                      int64_t* fault, hipStream_t st) {
+  if (S < 1 || S > 0x7fffffff || n < 0 || max_packet < 0 || mode < 0 ||
+      mode > 1 || (mode == 1 && nwr == nullptr))
     return (int)hipErrorInvalidValue;
   if (hipMemsetAsync(fault, 0, sizeof(int64_t), st) != hipSuccess) return -4;
   zk::front_table_k<<<zk::fg_blocks(S + 1), zk::FG_T, 0, st>>>(raw_starts, S,
                                                                n, fault);
   ZK_LAUNCH_CHECK();
-  zk::front_cut_k<<<(unsigned)S, zk::FC_T, 0, st>>>(
-      raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota, max_packet,
-      fault, take, nfr, flag);
+  if (mode == 1)
+    zk::front_cut_k<true><<<(unsigned)S, zk::FC_T, 0, st>>>(
+        raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota,
+        max_packet, fault, take, nfr, flag, has_acl, nwr);
+  else
+    zk::front_cut_k<false><<<(unsigned)S, zk::FC_T, 0, st>>>(
+        raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota,
+        max_packet, fault, take, nfr, flag, 0, nullptr);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+int zk_front_cut(const uint8_t* raw, int64_t n, const int64_t* raw_starts,
+                 int64_t S, int64_t quota, int64_t max_packet, int64_t* take,
+                 int32_t* nfr, int32_t* flag, int64_t* fault, hipStream_t st) {
+  return zk_front_cut_mode(raw, n, raw_starts, S, quota, max_packet, 0, 0, take,
+                           nfr, flag, nullptr, fault, st);
 }
 
 // The gather.  streams[4] / caps[4] (host arrays; a null stream has no
@@ -314,11 +351,14 @@ int zk_front_gather(const uint8_t* const* streams, const int64_t* caps,
 // caps[4] (host array: the four streams' bytes), owner[64] (workspace) ->
 // piece 4 s + k of connection s (p_stream / p_src / p_len [4 S]) and
 // stats[8]: [0] the segments that name a watcher slot another one owns.
-int zk_front_tx_pieces(const int64_t* rep_off, const int32_t* wslots,
-                       const int64_t* const* slot_off, const int32_t* err,
-                       const int64_t* caps, int64_t S, int64_t* owner,
-                       int32_t* p_stream, int64_t* p_src, int64_t* p_len,
-                       int64_t* stats, hipStream_t st) {
+// rep_end[S] (or null): connection s's replies end there instead of at
+// rep_off[s + 1] (the ordered serve's deferral).
+int zk_front_tx_pieces_end(const int64_t* rep_off, const int64_t* rep_end,
+                           const int32_t* wslots,
+                           const int64_t* const* slot_off, const int32_t* err,
+                           const int64_t* caps, int64_t S, int64_t* owner,
+                           int32_t* p_stream, int64_t* p_src, int64_t* p_len,
+                           int64_t* stats, hipStream_t st) {
   if (S < 1 || S > 0x1fffffff) return (int)hipErrorInvalidValue;
   zk::front_owner_k<<<1, zk::FG_T, 0, st>>>(wslots, S, owner, stats);
   ZK_LAUNCH_CHECK();
@@ -330,10 +370,24 @@ int zk_front_tx_pieces(const int64_t* rep_off, const int32_t* wslots,
   t.wslots = wslots;
   t.owner = owner;
   t.S = S;
-  zk::front_pieces_k<<<zk::fg_blocks(S), zk::FG_T, 0, st>>>(t, p_stream, p_src,
-                                                          p_len);
+  t.rep_end = rep_end;
+  if (rep_end != nullptr)
+    zk::front_pieces_k<true><<<zk::fg_blocks(S), zk::FG_T, 0, st>>>(
+        t, p_stream, p_src, p_len);
+  else
+    zk::front_pieces_k<false><<<zk::fg_blocks(S), zk::FG_T, 0, st>>>(
+        t, p_stream, p_src, p_len);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+int zk_front_tx_pieces(const int64_t* rep_off, const int32_t* wslots,
+                       const int64_t* const* slot_off, const int32_t* err,
+                       const int64_t* caps, int64_t S, int64_t* owner,
+                       int32_t* p_stream, int64_t* p_src, int64_t* p_len,
+                       int64_t* stats, hipStream_t st) {
+  return zk_front_tx_pieces_end(rep_off, nullptr, wslots, slot_off, err, caps,
+                                S, owner, p_stream, p_src, p_len, stats, st);
 }
 
 }  // extern "C"

@@ -308,8 +308,13 @@ struct ServeSegs {
   const int64_t* bad;        // [2] != 0: the table is unsound
   int64_t S;
 };
+// DEFER (MS only): the ordered serve with deferral (tree_order.hip
+// ord_clip_mark_k).  A deferred frame comes with no segment and the rank byte
+// ORD_RANK: it is refused like any frame of no segment, but the batch is not
+// refused as a whole, so the numbers of its other SEQUENTIAL creates are in
+// use and a deferred one leaves its gap in the parent's cversion.
 static_assert(TR_T == FR_T, "a workgroup per block of FR_T frames");
-template <bool PARSE, bool RO, bool TILES, bool MS = false>
+template <bool PARSE, bool RO, bool TILES, bool MS = false, bool DEFER = false>
 ZK_DEV void tree_serve_body(
     const ZkTree& t, const uint8_t* __restrict__ rx, const ZkReqOut& q,
     const int64_t* __restrict__ foff, const int32_t* __restrict__ flen,
@@ -545,7 +550,9 @@ ZK_DEV void tree_serve_body(
   // (MS, the whole batch refused: no number of the ordering pass's bump was
   // used, so the parent's cversion goes back with the child)
   if (numbered)
-    cn_add(t, seq_par(t, i), MS && ms_err == ERR_SYSTEM ? -1 : 0, -1);
+    cn_add(t, seq_par(t, i),
+           MS && ms_err == ERR_SYSTEM && !(DEFER && rk == ORD_RANK) ? -1 : 0,
+           -1);
   // ---- watches: reads with watch=1 arm (this session's slot), successful
   // writes fire (lib/zk-session.js:558-574 is the client side of the
   // trigger table; the server rules are SURVEY Appendix D)
@@ -605,7 +612,11 @@ ZK_DEV void tree_serve_body(
   // in the RO instance.)
   if (!RO) {
     wave_free(t, freed);
-    wave_mark_dirty(t, L.err == ERR_OK ? L.par : -1);
+    // (DEFER: a numbered create that was not made has moved its parent's
+    // child count in a pass of its own — the last, for a deferred frame — so
+    // the parent's Stat is written again behind it)
+    wave_mark_dirty(t, L.err == ERR_OK ? L.par
+                       : DEFER && numbered ? seq_par(t, i) : -1);
   }
   if (r_sizes != nullptr) {                       // block-uniform
     __shared__ int64_t sm[TR_T / 64 + 1];
@@ -686,6 +697,22 @@ __global__ __launch_bounds__(TR_T) void tree_serve_sess_k(
       nullptr, nullptr, nullptr, &M);
 }
 
+// The ordered passes of a session batch served with deferral (DEFER; K12's
+// table only).
+__global__ __launch_bounds__(TR_T) void tree_serve_sess_defer_k(
+    ZkTree t, const uint8_t* __restrict__ rx, ZkReqOut q,
+    const int64_t* __restrict__ n_dev, int64_t ncap, ZkServeOut o,
+    int64_t now_ms, const uint8_t* __restrict__ rank, int32_t pass,
+    int32_t last_pass, int64_t snap_base, int64_t snap_cap,
+    int64_t* __restrict__ snap_top, int64_t* __restrict__ fired,
+    ServeSegs M) {
+  tree_serve_body<false, false, false, true, true>(
+      t, rx, q, nullptr, nullptr, n_dev, ncap, o.opcode, o.xid, o.err, o.node,
+      o.zxid, o.path_off, o.path_len, o.slot, o.sizes, o.block_sums, 0,
+      now_ms, rank, pass, last_pass, snap_base, snap_cap, snap_top, -1, fired,
+      nullptr, nullptr, nullptr, &M);
+}
+
 // The one launch site of tree_serve_k (zk_tree.h ServeLaunch): its
 // <false, false>, <true, false> and <true, true> instances, and the two of
 // tree_serve_tiles_k.
@@ -712,6 +739,15 @@ int serve_launch(const ServeLaunch& s, hipStream_t st) {
       return -1;
     const ServeSegs M{s.f_seg, s.sessions, s.wslots, s.seg_state, s.bad,
                       s.nseg};
+    if (s.defer) {
+      if (parse || s.rank == nullptr) return -1;
+      tree_serve_sess_defer_k<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T,
+                                0, st>>>(
+          *s.tree, s.rx, *s.q, s.n_dev, s.ncap, o, s.now_ms, s.rank, s.pass,
+          s.last_pass, s.snap_base, s.snap_cap, s.snap_top, s.fired, M);
+      ZK_LAUNCH_CHECK();
+      return 0;
+    }
     const auto km = parse ? tree_serve_sess_k<true> : tree_serve_sess_k<false>;
     km<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T, 0, st>>>(
         *s.tree, s.rx, parse ? ZkReqOut{} : *s.q, s.foff, s.flen, s.n_dev,

@@ -1,6 +1,7 @@
 // The GPU tree's in-batch ordering pass and the ordered serve over it (the
 // tree: zk_tree.h; the serve kernel: tree.hip, through serve_launch).
 #include "zk_tree.h"
+#include "zk_order_clip.h"
 
 namespace zk {
 
@@ -223,6 +224,128 @@ __global__ __launch_bounds__(TR_T) void ord_rank_k(int64_t ncap, OrderWs w,
   }
 }
 
+// ---- deferral instead of refusal (ord_clip_*; the rules: zk_order_clip.h) ----
+// A session batch of any op mix behind a socket: a frame of the serve's class
+// whose rank the passes cannot reach, and everything after it in its
+// connection, leaves the batch before the first serve pass (its segment
+// becomes -1: every engine, the catch-up and the close pass refuse a frame of
+// no segment without effect) and stays pending with its connection.  Removing
+// requests only lowers the ranks of the rest (a rank is a longest chain over
+// earlier requests), so the rank bytes stay valid upper bounds and no
+// surviving frame has a rank >= passes.  All tables here are the WHOLE
+// batch's (cls / sub: the split's; f_seg: the assign's), nall its device
+// frame count; every index is checked against ncap and S.
+struct OrdClip {
+  const int32_t* cls;      // [ncap] the split's class per frame
+  const int32_t* sub;      // [ncap] its index in the class's table
+  const int64_t* nall;     // the whole batch's frame count
+  int32_t* f_seg;          // [ncap] frame -> segment (deferred: -1)
+  int32_t* seg_c[3];       // [ncap] each class's frame -> segment
+  int64_t* clipf;          // [S] first deferred frame (ncap: none)
+  int64_t* deferred;       // [1] frames deferred
+  const int64_t* bad;      // the table's fault word (or null): != 0, the batch
+  int64_t S;               // is refused as a whole and nothing is deferred
+};
+
+__global__ __launch_bounds__(TR_T) void ord_clip_init_k(OrdClip c,
+                                                        int64_t ncap) {
+  const int64_t s = (int64_t)blockIdx.x * TR_T + threadIdx.x;
+  if (s < c.S) c.clipf[s] = ncap;
+  if (s == 0) *c.deferred = 0;
+}
+
+// clipf[seg] = the smallest whole-batch index of an overflowing frame of seg.
+// The lanes of a wave that overflow are grouped by segment with a ballot
+// loop (wave-uniform; a segment's frames are contiguous, so a wave sees few):
+// the lowest lane of a group holds its minimum and issues the one atomicMin.
+__global__ __launch_bounds__(TR_T) void ord_clip_first_k(
+    OrdClip c, const uint8_t* __restrict__ rank, int64_t ncap,
+    int32_t passes) {
+  const int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int64_t nfr = *c.nall;
+  if (nfr > ncap) nfr = ncap;
+  int32_t seg = -1;
+  bool ov = false;
+  if (i < nfr) {
+    seg = c.f_seg[i];
+    ov = seg >= 0 && seg < c.S && (c.bad == nullptr || *c.bad == 0) &&
+         clip_overflow(c.cls[i], c.sub[i], rank, ncap, passes);
+  }
+  uint64_t m = __ballot(ov);
+  while (m != 0) {
+    const int l = __ffsll((unsigned long long)m) - 1;
+    const int32_t sl = __shfl(seg, l, 64);
+    const uint64_t same = __ballot(ov && seg == sl);
+    if (lane == l)
+      atomicMin((unsigned long long*)&c.clipf[sl], (unsigned long long)i);
+    m &= ~same;
+  }
+}
+
+// Frame i at or after its segment's clipf leaves the batch.  A frame of the
+// serve's class also gets the rank byte ORD_RANK (rank, when the ordered
+// serve follows): the last pass answers it, and the serve's DEFER instance
+// tells it from a frame of a batch refused as a whole (tree.hip: a deferred
+// SEQUENTIAL create keeps its number out of use, a gap in the parent's
+// cversion, where the whole refusal hands the numbers back).
+__global__ __launch_bounds__(TR_T) void ord_clip_mark_k(
+    OrdClip c, int64_t ncap, uint8_t* __restrict__ rank) {
+  const int64_t i = (int64_t)blockIdx.x * TR_T + threadIdx.x;
+  int64_t nfr = *c.nall;
+  if (nfr > ncap) nfr = ncap;
+  bool df = false;
+  if (i < nfr) {
+    df = clip_deferred(c.clipf, c.S, c.f_seg[i], i);
+    if (df) {
+      c.f_seg[i] = -1;
+      const int32_t k = c.cls[i], sb = c.sub[i];
+      if (k >= 0 && k < MIX_CLASSES && sb >= 0 && sb < ncap)
+        (k == 0 ? c.seg_c[0] : k == 1 ? c.seg_c[1] : c.seg_c[2])[sb] = -1;
+      if (k == MIX_A && sb >= 0 && sb < ncap && rank != nullptr)
+        rank[sb] = (uint8_t)ORD_RANK;
+    }
+  }
+  const uint64_t m = __ballot(df);
+  if (m != 0 && (threadIdx.x & 63) == 0)
+    atomicAdd((unsigned long long*)c.deferred,
+              (unsigned long long)__popcll((unsigned long long)m));
+}
+
+__global__ __launch_bounds__(TR_T) void ord_clip_ranges_k(
+    const int64_t* __restrict__ clipf, const int64_t* __restrict__ rep_off,
+    const int64_t* __restrict__ rec_off, const int64_t* __restrict__ off,
+    const int64_t* __restrict__ starts, const int64_t* __restrict__ nall,
+    int64_t ncap, int64_t S, int64_t* __restrict__ rep_end,
+    int64_t* __restrict__ used) {
+  const int64_t s = (int64_t)blockIdx.x * TR_T + threadIdx.x;
+  if (s >= S) return;
+  int64_t nfr = *nall;
+  if (nfr > ncap) nfr = ncap;
+  const ClipRange r = clip_range(clipf, rep_off, rec_off, off, starts, nfr, s);
+  rep_end[s] = r.rep_end;
+  used[s] = r.used;
+}
+
+static_assert(CLIP_RANK == ORD_RANK, "zk_order_clip.h: the rank bits");
+
+// mark_rank: the rank table is the ordered serve's own (not a caller's).
+int clip_launch(const OrdClip& c, uint8_t* rank, int64_t ncap,
+                int32_t passes, bool mark_rank, hipStream_t st) {
+  if (ncap < 1 || ncap > 0x7fffffff || c.S < 1 || c.S > 0x7fffffff ||
+      passes < 1)
+    return -1;
+  const unsigned nb = (unsigned)((ncap + TR_T - 1) / TR_T);
+  ord_clip_init_k<<<(unsigned)((c.S + TR_T - 1) / TR_T), TR_T, 0, st>>>(c,
+                                                                        ncap);
+  ZK_LAUNCH_CHECK();
+  ord_clip_first_k<<<nb, TR_T, 0, st>>>(c, rank, ncap, passes);
+  ZK_LAUNCH_CHECK();
+  ord_clip_mark_k<<<nb, TR_T, 0, st>>>(c, ncap, mark_rank ? rank : nullptr);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
 int bscan_launch(int64_t* bsum, int64_t nb, hipStream_t st) {
   ord_bscan_k<<<1, ORD_SCAN_T, 0, st>>>(bsum, nb);
   ZK_LAUNCH_CHECK();
@@ -293,7 +416,8 @@ static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
                          int64_t now_ms, uint8_t* ws, int64_t ws_bytes,
                          int32_t passes, int64_t snap_base, int64_t snap_cap,
                          int32_t wslot, int64_t* fired,
-                         const zk::ServeLaunch* segs, hipStream_t st) {
+                         const zk::ServeLaunch* segs, hipStream_t st,
+                         const zk::OrdClip* clip = nullptr) {
   if (ncap <= 0) return 0;
   if (ncap > zk::ORD_FM) return -1;          // packed group counts
   if (passes < 1 || passes > zk::ORD_RANK) return -1;
@@ -323,6 +447,11 @@ static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
   }
   zk::ord_rank_k<<<nb, zk::TR_T, 0, st>>>(ncap, w, rank);
   ZK_LAUNCH_CHECK();
+  if (clip != nullptr) {
+    // deferral: the frames the passes cannot reach leave the batch
+    rc = zk::clip_launch(*clip, rank, ncap, passes, true, st);
+    if (rc) return rc;
+  }
   zk::ServeLaunch s;
   s.tree = t, s.rx = rx, s.q = q, s.n_dev = n_dev, s.ncap = ncap;
   s.out = out, s.session = session, s.now_ms = now_ms, s.rank = rank;
@@ -332,6 +461,7 @@ static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
     s.f_seg = segs->f_seg, s.sessions = segs->sessions;
     s.wslots = segs->wslots, s.seg_state = segs->seg_state;
     s.bad = segs->bad, s.nseg = segs->nseg;
+    s.defer = clip != nullptr;
   }
   for (s.pass = 0; s.pass < passes; ++s.pass) {
     const int32_t last = s.pass == passes - 1;
@@ -373,6 +503,75 @@ int zk_tree_serve_ordered_sessions(
   m.seg_state = seg_state, m.bad = bad, m.nseg = nseg;
   return ordered_serve(t, rx, q, n_dev, ncap, out, 0, now_ms, ws, ws_bytes,
                        passes, snap_base, snap_cap, -1, fired, &m, st);
+}
+
+// zk_tree_serve_ordered_sessions for the serve's class of a session batch of
+// any op mix, with deferral in place of the rank refusal (ord_clip_* above;
+// the rules: zk_order_clip.h).  (rx .. nseg) as there, over the class's
+// compacted frames: f_seg is seg_c0.  Then the WHOLE batch's tables: the
+// split's cls / sub [ncap], its frame count nall, the assign's f_seg_all
+// [ncap] and the three classes' segment tables -> the deferred frames'
+// entries of f_seg_all / seg_c* become -1, clipf[nseg] (per segment the first
+// deferred whole-batch frame; ncap: none) and deferred[1] (frames deferred).
+// Three launches between the ranking and the first pass; no host read.
+int zk_tree_serve_ordered_sessions_defer(
+    const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
+    const int64_t* n_dev, int64_t ncap, const ZkServeOut* out, int64_t now_ms,
+    uint8_t* ws, int64_t ws_bytes, int32_t passes, int64_t snap_base,
+    int64_t snap_cap, int64_t* fired, const int64_t* sessions,
+    const int32_t* wslots, const int32_t* seg_state, const int64_t* bad,
+    int64_t nseg, const int32_t* cls, const int32_t* sub, const int64_t* nall,
+    int32_t* f_seg_all, int32_t* seg_c0, int32_t* seg_c1, int32_t* seg_c2,
+    int64_t* clipf, int64_t* deferred, hipStream_t st) {
+  if (seg_c0 == nullptr || seg_c1 == nullptr || seg_c2 == nullptr ||
+      cls == nullptr || sub == nullptr || nall == nullptr ||
+      f_seg_all == nullptr || clipf == nullptr || deferred == nullptr ||
+      nseg < 1)
+    return (int)hipErrorInvalidValue;
+  zk::ServeLaunch m;
+  m.f_seg = seg_c0, m.sessions = sessions, m.wslots = wslots;
+  m.seg_state = seg_state, m.bad = bad, m.nseg = nseg;
+  zk::OrdClip c;
+  c.cls = cls, c.sub = sub, c.nall = nall, c.f_seg = f_seg_all;
+  c.seg_c[0] = seg_c0, c.seg_c[1] = seg_c1, c.seg_c[2] = seg_c2;
+  c.clipf = clipf, c.deferred = deferred, c.S = nseg, c.bad = bad;
+  return ordered_serve(t, rx, q, n_dev, ncap, out, 0, now_ms, ws, ws_bytes,
+                       passes, snap_base, snap_cap, -1, fired, &m, st, &c);
+}
+
+// The deferral stage alone (the three launches), over a rank table of the
+// caller's: rank[ncap], the rest as zk_tree_serve_ordered_sessions_defer.
+int zk_order_clip(const uint8_t* rank, int32_t passes, const int32_t* cls,
+                  const int32_t* sub, const int64_t* nall, int64_t ncap,
+                  int32_t* f_seg_all, int32_t* seg_c0, int32_t* seg_c1,
+                  int32_t* seg_c2, int64_t* clipf, int64_t* deferred,
+                  int64_t nseg, hipStream_t st) {
+  if (rank == nullptr || nseg < 1 || ncap < 1)
+    return (int)hipErrorInvalidValue;
+  zk::OrdClip c;
+  c.cls = cls, c.sub = sub, c.nall = nall, c.f_seg = f_seg_all;
+  c.seg_c[0] = seg_c0, c.seg_c[1] = seg_c1, c.seg_c[2] = seg_c2;
+  c.clipf = clipf, c.deferred = deferred, c.S = nseg, c.bad = nullptr;
+  // (the caller's rank table is only read)
+  return zk::clip_launch(c, const_cast<uint8_t*>(rank), ncap, passes, false,
+                         st);
+}
+
+// After the merge and zk_sess_ranges: per segment where its replies end and
+// how many of its request bytes were consumed (zk_order_clip.h clip_range).
+// clipf[S], rep_off[S + 1], the merged rec_off[ncap], the whole batch's frame
+// table off[ncap] and count nall, starts[S + 1] -> rep_end[S], used[S].
+int zk_order_clip_ranges(const int64_t* clipf, const int64_t* rep_off,
+                         const int64_t* rec_off, const int64_t* off,
+                         const int64_t* starts, const int64_t* nall,
+                         int64_t ncap, int64_t S, int64_t* rep_end,
+                         int64_t* used, hipStream_t st) {
+  if (S < 1 || S > 0x7fffffff || ncap < 0) return (int)hipErrorInvalidValue;
+  zk::ord_clip_ranges_k<<<(unsigned)((S + zk::TR_T - 1) / zk::TR_T), zk::TR_T,
+                          0, st>>>(clipf, rep_off, rec_off, off, starts, nall,
+                                   ncap, S, rep_end, used);
+  ZK_LAUNCH_CHECK();
+  return 0;
 }
 
 // Byte offset in the ordering workspace of {max rank, scratch bytes used}

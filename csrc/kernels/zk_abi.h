@@ -558,6 +558,39 @@ int zk_front_gather(const uint8_t* const*, const int64_t*, const int32_t*,
 int zk_front_tx_pieces(const int64_t*, const int32_t*, const int64_t* const*,
                        const int32_t*, const int64_t*, int64_t, int64_t*,
                        int32_t*, int64_t*, int64_t*, int64_t*, hipStream_t);
+// The front end in front of the ordered session serve.  zk_front_cut_mode:
+// zk_front_cut with (mode, has_acl) after max_packet and nwr[S] after flag;
+// mode 0 is zk_front_cut (nwr null), mode 1 the ordered rule
+// (zk_front.h front_walk_ordered).  zk_front_tx_pieces_end: zk_front_tx_pieces
+// with rep_end[S] (or null) after rep_off.
+int zk_front_cut_mode(const uint8_t*, int64_t, const int64_t*, int64_t,
+                      int64_t, int64_t, int32_t, int32_t, int64_t*, int32_t*,
+                      int32_t*, int32_t*, int64_t*, hipStream_t);
+int zk_front_tx_pieces_end(const int64_t*, const int64_t*, const int32_t*,
+                           const int64_t* const*, const int32_t*,
+                           const int64_t*, int64_t, int64_t*, int32_t*,
+                           int64_t*, int64_t*, int64_t*, hipStream_t);
+// Deferral in the ordered session serve (tree_order.hip ord_clip_*; the rules:
+// zk_order_clip.h).  zk_tree_serve_ordered_sessions_defer:
+// zk_tree_serve_ordered_sessions over the serve's class of a batch of any op
+// mix (f_seg is seg_c0 below), then the whole batch's (cls, sub, count,
+// f_seg, seg_c0 / c1 / c2) and clipf[S], deferred[1].  zk_order_clip: the
+// stage alone over (rank[ncap], passes, cls, sub, count, ncap, f_seg, seg_c0 /
+// c1 / c2, clipf, deferred, S).  zk_order_clip_ranges: (clipf, rep_off[S + 1],
+// the merged rec_off, the frames' off, starts[S + 1], count, ncap, S) ->
+// rep_end[S], used[S].
+int zk_tree_serve_ordered_sessions_defer(
+    const ZkTree*, const uint8_t*, const ZkReqOut*, const int64_t*, int64_t,
+    const ZkServeOut*, int64_t, uint8_t*, int64_t, int32_t, int64_t, int64_t,
+    int64_t*, const int64_t*, const int32_t*, const int32_t*, const int64_t*,
+    int64_t, const int32_t*, const int32_t*, const int64_t*, int32_t*,
+    int32_t*, int32_t*, int32_t*, int64_t*, int64_t*, hipStream_t);
+int zk_order_clip(const uint8_t*, int32_t, const int32_t*, const int32_t*,
+                  const int64_t*, int64_t, int32_t*, int32_t*, int32_t*,
+                  int32_t*, int64_t*, int64_t*, int64_t, hipStream_t);
+int zk_order_clip_ranges(const int64_t*, const int64_t*, const int64_t*,
+                         const int64_t*, const int64_t*, const int64_t*,
+                         int64_t, int64_t, int64_t*, int64_t*, hipStream_t);
 }  // extern "C"
 
 // Layout pins (LP64 on both sides: pointers and int64_t are 8 bytes).

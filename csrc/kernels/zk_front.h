@@ -6,8 +6,10 @@
 //                       served this tick: whole frames only, a bad length ends
 //                       the connection, at most `quota` frames, and either any
 //                       number of non-write frames or exactly one write frame
-//                       (serve_sessions_mixed has no in-batch ordering, and a
-//                       connection's requests take effect in order)
+//                       (the unordered session serve has no in-batch ordering,
+//                       and a connection's requests take effect in order)
+//   front_walk_ordered  the same in front of the ordered session serve: writes
+//                       no longer end the run, the engines' fixed sequence does
 //   front_boundary_bad  what makes the table of the raw stream's segments
 //                       unsound
 //   front_owner_scan,   which connection gets a watcher slot's notification
@@ -57,6 +59,63 @@ ZK_HD FrontCut front_walk(int64_t len, int64_t quota, int64_t max_packet,
     p += 4 + (int64_t)L;
     ++c.nfr;
     if (wr) break;
+  }
+  c.take = p;
+  return c;
+}
+
+// ---- the ordered cut ----------------------------------------------------------
+// With the ordered session serve behind it (serve_sessions_mixed(ordered=True))
+// a connection's writes of one batch take effect in its own order, so the run
+// is no longer cut at a write.  What stays out of order inside a batch is the
+// engines' fixed sequence: the list and GET_ACL engines and the SET_WATCHES
+// catch-up see the tree after all the batch's writes, and the close pass runs
+// after everything.  The run is the longest prefix for which that sequence is
+// the connection's own order:
+//   phase 0  frames of the serve's class, writes included;
+//   phase 1  from the first GET_CHILDREN / GET_CHILDREN2 / GET_ACL (zk_mix.h's
+//            class rule: GET_ACL only on a tree with an ACL table) or
+//            SET_WATCHES frame on: a CREATE / DELETE / SET_DATA ends the run
+//            before it;
+//   a CLOSE_SESSION ends the run after itself.
+ZK_HD bool front_is_tree_write(int32_t op) {
+  return op == OP_CREATE || op == OP_DELETE || op == OP_SET_DATA;
+}
+
+ZK_HD bool front_is_late(int32_t op, bool has_acl) {
+  return op == OP_GET_CHILDREN || op == OP_GET_CHILDREN2 ||
+         (op == OP_GET_ACL && has_acl) || op == OP_SET_WATCHES;
+}
+
+// nwr: the write frames (front_is_write) among the nfr taken.
+struct FrontCutOrd {
+  int64_t take;
+  int32_t nfr, flag, nwr;
+};
+
+// front_walk's contract for rd; the phase is one more word of the state.
+template <class Rd>
+ZK_HD FrontCutOrd front_walk_ordered(int64_t len, int64_t quota,
+                                     int64_t max_packet, bool has_acl,
+                                     Rd&& rd) {
+  FrontCutOrd c{0, 0, 0, 0};
+  if (quota > 0x7fffffff) quota = 0x7fffffff;
+  int64_t p = 0;
+  int32_t phase = 0;
+  while (c.nfr < quota && len - p >= 4) {
+    const int32_t L = rd(p);
+    if (L < 0 || L > max_packet) {
+      c.flag = 1;
+      break;
+    }
+    if (L > len - p - 4) break;                    // the body is not whole yet
+    const int32_t op = L >= 8 ? rd(p + 8) : 0;     // (0 is no opcode)
+    if (phase == 1 && front_is_tree_write(op)) break;
+    if (front_is_late(op, has_acl)) phase = 1;
+    p += 4 + (int64_t)L;
+    ++c.nfr;
+    if (front_is_write(op)) ++c.nwr;
+    if (op == OP_CLOSE_SESSION) break;
   }
   c.take = p;
   return c;
@@ -122,6 +181,11 @@ struct FrontTx {
   const int32_t* wslots;         // [S]
   const int64_t* owner;          // [64] front_owner_scan's verdicts
   int64_t S;
+  // [S] or null: connection s's replies end at rep_end[s], not rep_off[s + 1]
+  // (the ordered serve's deferral: zk_order_clip.h clip_range).  The plain
+  // front_pieces_k instance never reads it: its registers and code are what
+  // they were, its kernel arguments are these 8 bytes longer.
+  const int64_t* rep_end = nullptr;
 };
 
 struct FrontPiece {
@@ -139,13 +203,17 @@ ZK_HD FrontPiece front_slice(int32_t stream, int64_t a, int64_t b,
 
 // Piece k (0..3) of connection s < S.  Replies whatever its watcher slot is;
 // slot w's slices only for a w in 0..63 whose owner is s.  rep_off is read at
-// s and s + 1, a slot_off at w and w + 1, owner at w only.
+// s and s + 1, a slot_off at w and w + 1, owner at w only; rep_end (END
+// instances, when there) at s only.
+template <bool END = true>
 ZK_HD FrontPiece front_piece(const FrontTx& t, int64_t s, int32_t k) {
   const FrontPiece none{k, 0, 0};
   if (s < 0 || s >= t.S || k < 0 || k >= FRONT_PIECES) return none;
   if (t.err != nullptr && *t.err != 0) return none;
   if (k == FS_REPLY) {
     if (t.rep_off == nullptr) return none;
+    if (END && t.rep_end != nullptr)
+      return front_slice(k, t.rep_off[s], t.rep_end[s], t.cap[0]);
     return front_slice(k, t.rep_off[s], t.rep_off[s + 1], t.cap[0]);
   }
   const int64_t* so = t.slot_off[k - 1];

@@ -899,6 +899,9 @@ struct ServeLaunch {
   const int32_t* seg_state = nullptr;
   const int64_t* bad = nullptr;
   int64_t nseg = 0;
+  // the ordered passes of a session batch served with deferral (q and rank
+  // set): the MS instance that keeps a deferred SEQUENTIAL create's number
+  int32_t defer = 0;
 };
 int serve_launch(const ServeLaunch& s, hipStream_t st);
 

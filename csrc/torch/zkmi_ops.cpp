@@ -965,6 +965,111 @@ void tree_serve_ordered_sessions(
          "tree_serve_ordered_sessions");
 }
 
+// tree_serve_ordered_sessions over the serve's class of a session batch of any
+// op mix, with deferral (zk_order_clip.h): seg_c[0] is the class's f_seg; cls /
+// sub / count_all / f_seg_all are the whole batch's.
+void tree_serve_ordered_sessions_defer(
+    const std::vector<Tensor>& t, const Tensor& rx,
+    const std::vector<Tensor>& q, const Tensor& n_dev, int64_t ncap,
+    const std::vector<Tensor>& r, int64_t now_ms, const Tensor& ws,
+    int64_t passes, const c10::optional<Tensor>& scratch,
+    const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
+    const Tensor& sessions, const Tensor& wslots, const Tensor& seg_state,
+    const Tensor& bad, const Tensor& cls, const Tensor& sub,
+    const Tensor& count_all, const Tensor& f_seg_all,
+    const std::vector<Tensor>& seg_c, const Tensor& clipf,
+    const Tensor& deferred) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
+  ZkReqOut qo = req_out(q, ncap, d);
+  ZkServeOut ro = serve_out(r, ncap, d);
+  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
+  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1, "zkmi: ncap");
+  need(seg_c, 3, "seg_c");
+  const int64_t need_ws = zk_tree_order_workspace(ncap);
+  uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
+  int64_t snap_base = 0, snap_cap = 0;
+  if (scratch.has_value() && scratch->defined()) {
+    const Tensor& sc = *scratch;
+    P<uint8_t>(sc, U8, 0, "scratch", d);
+    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
+                "zkmi: scratch must be a view of the tree's slab");
+    snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
+                          (const uint8_t*)t[6].data_ptr());
+    TORCH_CHECK(snap_base >= s.slab_cap && snap_base % 16 == 0,
+                "zkmi: scratch must start 16-aligned past the tree's slab");
+    snap_cap = sc.numel();
+  }
+  const SegPtrs m =
+      seg_ptrs(seg_c[0], sessions, wslots, seg_state, bad, ncap, d);
+  hip_ok(zk_tree_serve_ordered_sessions_defer(
+             &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms, w,
+             ws.numel(), (int32_t)passes, snap_base, snap_cap,
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.sessions,
+             m.wslots, m.seg_state, m.bad, m.S,
+             P<int32_t>(cls, I32, ncap, "cls", d),
+             P<int32_t>(sub, I32, ncap, "sub", d),
+             P<int64_t>(count_all, I64, 1, "count_all", d),
+             P<int32_t>(f_seg_all, I32, ncap, "f_seg_all", d),
+             P<int32_t>(seg_c[0], I32, ncap, "seg_c[0]", d),
+             P<int32_t>(seg_c[1], I32, ncap, "seg_c[1]", d),
+             P<int32_t>(seg_c[2], I32, ncap, "seg_c[2]", d),
+             P<int64_t>(clipf, I64, m.S, "clipf", d),
+             P<int64_t>(deferred, I64, 1, "deferred", d), cur_stream()),
+         "tree_serve_ordered_sessions_defer");
+}
+
+// The deferral stage alone over a rank table of the caller's (uint8 [ncap]).
+void order_clip(const Tensor& rank, int64_t passes, const Tensor& cls,
+                const Tensor& sub, const Tensor& count_all, int64_t ncap,
+                const Tensor& f_seg_all, const std::vector<Tensor>& seg_c,
+                const Tensor& clipf, const Tensor& deferred) {
+  const Tensor* d = &rank;
+  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
+  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1, "zkmi: order_clip ncap");
+  need(seg_c, 3, "seg_c");
+  const int64_t S = clipf.numel();
+  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  hip_ok(zk_order_clip(P<uint8_t>(rank, U8, ncap, "rank"), (int32_t)passes,
+                       P<int32_t>(cls, I32, ncap, "cls", d),
+                       P<int32_t>(sub, I32, ncap, "sub", d),
+                       P<int64_t>(count_all, I64, 1, "count_all", d), ncap,
+                       P<int32_t>(f_seg_all, I32, ncap, "f_seg_all", d),
+                       P<int32_t>(seg_c[0], I32, ncap, "seg_c[0]", d),
+                       P<int32_t>(seg_c[1], I32, ncap, "seg_c[1]", d),
+                       P<int32_t>(seg_c[2], I32, ncap, "seg_c[2]", d),
+                       P<int64_t>(clipf, I64, S, "clipf", d),
+                       P<int64_t>(deferred, I64, 1, "deferred", d), S,
+                       cur_stream()),
+         "order_clip");
+}
+
+// rep_end / used [S] after the merge and sess_ranges.
+void order_clip_ranges(const Tensor& clipf, const Tensor& rep_off,
+                       const Tensor& rec_off, const Tensor& frame_off,
+                       const Tensor& starts, const Tensor& count_all,
+                       int64_t ncap, const Tensor& rep_end,
+                       const Tensor& used) {
+  const Tensor* d = &clipf;
+  const int64_t S = clipf.numel();
+  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  TORCH_CHECK(ncap >= 0, "zkmi: order_clip_ranges ncap");
+  hip_ok(zk_order_clip_ranges(
+             P<int64_t>(clipf, I64, S, "clipf"),
+             P<int64_t>(rep_off, I64, S + 1, "rep_off", d),
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(frame_off, I64, ncap, "frame_off", d),
+             P<int64_t>(starts, I64, S + 1, "starts", d),
+             P<int64_t>(count_all, I64, 1, "count_all", d), ncap, S,
+             P<int64_t>(rep_end, I64, S, "rep_end", d),
+             P<int64_t>(used, I64, S, "used", d), cur_stream()),
+         "order_clip_ranges");
+}
+
 // rep_off [S + 1] from the reply encode's rec_off; with slot_first, slot_off
 // [65] from the grouped notification encode's.
 void sess_ranges(const Tensor& first, const Tensor& rec_off,
@@ -1996,8 +2101,12 @@ int64_t front_chunk() { return zk_front_chunk(); }
 // The cut: raw[:n] with raw_starts [S + 1] -> take / nfr / flag [S], fault.
 void front_cut(const Tensor& raw, int64_t n, const Tensor& raw_starts,
                int64_t quota, int64_t max_packet, const Tensor& take,
-               const Tensor& nfr, const Tensor& flag, const Tensor& fault) {
+               const Tensor& nfr, const Tensor& flag, const Tensor& fault,
+               int64_t mode, bool has_acl, const c10::optional<Tensor>& nwr) {
   const Tensor* d = &raw;
+  TORCH_CHECK(mode == 0 || mode == 1, "zkmi: front_cut mode is 0 or 1");
+  TORCH_CHECK(mode == 0 || (nwr.has_value() && nwr->defined()),
+              "zkmi: front_cut mode 1 writes nwr");
   const int64_t S = raw_starts.numel() - 1;
   TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
               "zkmi: a segment table has at least one segment");
@@ -2005,12 +2114,25 @@ void front_cut(const Tensor& raw, int64_t n, const Tensor& raw_starts,
               ", raw holds ", raw.numel());
   TORCH_CHECK(max_packet >= 0 && max_packet < (1ll << 31),
               "zkmi: front_cut max_packet");
-  hip_ok(zk_front_cut(P<uint8_t>(raw, U8, std::max<int64_t>(n, 1), "raw"), n,
-                      P<int64_t>(raw_starts, I64, S + 1, "raw_starts", d), S,
-                      quota, max_packet, P<int64_t>(take, I64, S, "take", d),
-                      P<int32_t>(nfr, I32, S, "nfr", d),
-                      P<int32_t>(flag, I32, S, "flag", d),
-                      P<int64_t>(fault, I64, 1, "fault", d), cur_stream()),
+  if (mode == 0) {
+    hip_ok(zk_front_cut(P<uint8_t>(raw, U8, std::max<int64_t>(n, 1), "raw"), n,
+                        P<int64_t>(raw_starts, I64, S + 1, "raw_starts", d), S,
+                        quota, max_packet, P<int64_t>(take, I64, S, "take", d),
+                        P<int32_t>(nfr, I32, S, "nfr", d),
+                        P<int32_t>(flag, I32, S, "flag", d),
+                        P<int64_t>(fault, I64, 1, "fault", d), cur_stream()),
+           "front_cut");
+    return;
+  }
+  hip_ok(zk_front_cut_mode(
+             P<uint8_t>(raw, U8, std::max<int64_t>(n, 1), "raw"), n,
+             P<int64_t>(raw_starts, I64, S + 1, "raw_starts", d), S, quota,
+             max_packet, (int32_t)mode, has_acl ? 1 : 0,
+             P<int64_t>(take, I64, S, "take", d),
+             P<int32_t>(nfr, I32, S, "nfr", d),
+             P<int32_t>(flag, I32, S, "flag", d),
+             P<int32_t>(*nwr, I32, S, "nwr", d),
+             P<int64_t>(fault, I64, 1, "fault", d), cur_stream()),
          "front_cut");
 }
 
@@ -2049,7 +2171,8 @@ void front_tx_pieces(const c10::optional<Tensor>& rep_off,
                      const c10::optional<Tensor>& err,
                      std::vector<int64_t> caps, const Tensor& owner,
                      const Tensor& p_stream, const Tensor& p_src,
-                     const Tensor& p_len, const Tensor& stats) {
+                     const Tensor& p_len, const Tensor& stats,
+                     const c10::optional<Tensor>& rep_end) {
   const Tensor* d = &wslots;
   const int64_t S = wslots.numel();
   TORCH_CHECK(S >= 1 && S < (1ll << 29),
@@ -2059,8 +2182,9 @@ void front_tx_pieces(const c10::optional<Tensor>& rep_off,
       Popt<int64_t>(resume_off, I64, 65, "resume_off", d),
       Popt<int64_t>(notif_off, I64, 65, "notif_off", d),
       Popt<int64_t>(close_off, I64, 65, "close_off", d)};
-  hip_ok(zk_front_tx_pieces(
+  hip_ok(zk_front_tx_pieces_end(
              Popt<int64_t>(rep_off, I64, S + 1, "rep_off", d),
+             Popt<int64_t>(rep_end, I64, S, "rep_end", d),
              P<int32_t>(wslots, I32, S, "wslots"), so,
              Popt<int32_t>(err, I32, 1, "err", d), caps.data(), S,
              P<int64_t>(owner, I64, 64, "owner", d),
@@ -2188,6 +2312,21 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(d!)? fired, Tensor? seqno, Tensor f_seg, Tensor sessions, "
         "Tensor wslots, Tensor seg_state, Tensor bad) -> ()",
         &tree_serve_ordered_sessions);
+  m.def("tree_serve_ordered_sessions_defer(Tensor(a!)[] tree, Tensor rx, "
+        "Tensor[] requests, Tensor count, int ncap, Tensor(b!)[] out, "
+        "int now_ms, Tensor(c!) ws, int passes, Tensor? scratch, "
+        "Tensor(d!)? fired, Tensor? seqno, Tensor sessions, Tensor wslots, "
+        "Tensor seg_state, Tensor bad, Tensor cls, Tensor sub, "
+        "Tensor count_all, Tensor(e!) f_seg_all, Tensor(f!)[] seg_c, "
+        "Tensor(g!) clipf, Tensor(h!) deferred) -> ()",
+        &tree_serve_ordered_sessions_defer);
+  m.def("order_clip(Tensor rank, int passes, Tensor cls, Tensor sub, "
+        "Tensor count_all, int ncap, Tensor(a!) f_seg_all, "
+        "Tensor(b!)[] seg_c, Tensor(c!) clipf, Tensor(d!) deferred) -> ()",
+        &order_clip);
+  m.def("order_clip_ranges(Tensor clipf, Tensor rep_off, Tensor rec_off, "
+        "Tensor frame_off, Tensor starts, Tensor count_all, int ncap, "
+        "Tensor(a!) rep_end, Tensor(b!) used) -> ()", &order_clip_ranges);
   m.def("sess_ranges(Tensor first, Tensor rec_off, Tensor count, int ncap, "
         "Tensor total, Tensor err, Tensor(a!) rep_off, "
         "Tensor? slot_first=None, Tensor? ev_rec_off=None, "
@@ -2345,12 +2484,14 @@ TORCH_LIBRARY(zkmi, m) {
   m.def("front_chunk() -> int", &front_chunk);
   m.def("front_cut(Tensor raw, int n, Tensor raw_starts, int quota, "
         "int max_packet, Tensor(a!) take, Tensor(b!) nfr, Tensor(c!) flag, "
-        "Tensor(d!) fault) -> ()", &front_cut);
+        "Tensor(d!) fault, int mode=0, bool has_acl=False, "
+        "Tensor(e!)? nwr=None) -> ()", &front_cut);
   m.def("front_gather(Tensor[] streams, Tensor? p_stream, Tensor p_src, "
         "Tensor p_off, int P, Tensor(a!) dst, Tensor(b!) over) -> ()",
         &front_gather);
   m.def("front_tx_pieces(Tensor? rep_off, Tensor wslots, Tensor? resume_off, "
         "Tensor? notif_off, Tensor? close_off, Tensor? err, int[] caps, "
         "Tensor(a!) owner, Tensor(b!) p_stream, Tensor(c!) p_src, "
-        "Tensor(d!) p_len, Tensor(e!) stats) -> ()", &front_tx_pieces);
+        "Tensor(d!) p_len, Tensor(e!) stats, Tensor? rep_end=None) -> ()",
+        &front_tx_pieces);
 }

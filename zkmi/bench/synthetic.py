@@ -638,6 +638,29 @@ class SessionSegments(object):
         self.S = S
 
 
+class OrderDefer(object):
+    """Where ``serve_sessions_mixed(ordered=True, defer=...)`` leaves what it
+    deferred, for a table of ``S`` segments; all device tensors, nothing is
+    read back:
+
+    ``clipf``     int64 [S]: the first deferred frame of segment s, an index
+                  in the whole batch's frame table (``cap_frames``: none);
+    ``rep_end``   int64 [S]: connection s's replies are ``out[rep_off[s]:
+                  rep_end[s]]`` (the placeholders of its deferred frames lie
+                  behind and are never sent);
+    ``used``      int64 [S]: the request bytes of segment s that were
+                  consumed; the rest, from its first deferred frame on, is to
+                  be sent again in the next batch;
+    ``deferred``  int64 [1]: the frames deferred."""
+
+    def __init__(self, S, device):
+        self.S = int(S)
+        self.clipf = torch.zeros(self.S, dtype=I64, device=device)
+        self.rep_end = torch.zeros(self.S, dtype=I64, device=device)
+        self.used = torch.zeros(self.S, dtype=I64, device=device)
+        self.deferred = torch.zeros(1, dtype=I64, device=device)
+
+
 class _SegState(object):
     """What :meth:`GpuServer.serve_sessions` leaves on the device about the
     last session batch's segments."""
@@ -1153,8 +1176,8 @@ class GpuServer(object):
 
         The list ops and GET_ACL are not served here (UNIMPLEMENTED): a
         session batch that mixes them in goes through
-        :meth:`serve_sessions_mixed`.  Single-session still: the ordered
-        mixed batch.  How a connection's notification slices are
+        :meth:`serve_sessions_mixed` (``ordered`` there as here, for the
+        serve's class).  How a connection's notification slices are
         interleaved with its reply slice on the socket is the front end's
         business.
 
@@ -1721,7 +1744,8 @@ class GpuServer(object):
 
     def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
                              max_frame=None, out=None, resume=False,
-                             close=False):
+                             close=False, ordered=False, passes=4,
+                             defer=None):
         """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
         connections of :class:`SessionSegments` ``segs``, whatever ops they
         mix, as ONE batch: :meth:`serve_sessions` for every op of
@@ -1784,7 +1808,38 @@ class GpuServer(object):
         after the ``resume`` catch-up, so a list or a GET_ACL of the batch
         still sees a closing connection's ephemerals.
 
-        Not offered: in-batch ordering (``serve_sessions(ordered=True)``).
+        ``ordered``: the serve's class goes through the ordered session serve
+        (``serve_sessions(ordered=True)``: K12's request table over the
+        class's frames, the ranking, ``passes`` serve launches), so requests
+        of the serve's class that conflict (zk_tree_serve_ordered's rule: the
+        same path with a writer among them, a create / delete and its
+        parent's path) are applied as a serial execution in batch order
+        would, whichever segments they come from; a read that a later write
+        of the batch overtakes is answered from a snapshot (a tree with a
+        scratch tail).  GET_ACL and the list ops still run after the serve,
+        over the tree as all the batch's writes leave it, and the catch-up
+        and the close pass keep their place: in-batch order covers the
+        serve's class only.  :meth:`order_stats` works after the call.  A
+        request whose rank is >= ``passes`` is answered SYSTEMERROR, without
+        effect, as in :meth:`serve_sessions`.
+
+        ``defer`` (an :class:`OrderDefer` of ``segs.S`` segments; only with
+        ``ordered``): deferral instead of that refusal.  The frame whose rank
+        the passes cannot reach and every later frame of its segment, of any
+        class, leave the batch before the first pass: they are frames of no
+        segment, so nothing of them is parsed, looked up, claimed, armed,
+        fired, closed or caught up, and their SYSTEMERROR placeholders lie
+        behind ``defer.rep_end[s]`` in the segment's slice.  The caller
+        sends ``out[rep_off[s]:rep_end[s]]`` and serves the segment's bytes
+        from ``defer.used[s]`` on again in a later batch.  The frames that
+        stay are served as if the deferred ones had not been sent.  (A
+        deferred SEQUENTIAL create has taken its number, which stays out of
+        use: a gap in the parent's cversion, as every refused numbered create
+        leaves — the serve's instance for these passes does not hand a
+        deferred frame's number back as a batch refused as a whole does, so
+        the name it gets in a later batch is past every name of this one.  A
+        batch whose table is unsound is refused as a whole and defers
+        nothing.)
 
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
@@ -1801,6 +1856,12 @@ class GpuServer(object):
         if resume and tree.watch is None:
             raise ValueError('serve_sessions_mixed: resume needs a watch '
                              'table')
+        if defer is not None:
+            if not ordered:
+                raise ValueError('serve_sessions_mixed: defer needs ordered')
+            if not isinstance(defer, OrderDefer) or defer.S != segs.S:
+                raise ValueError('serve_sessions_mixed: defer is an '
+                                 'OrderDefer of segs.S segments')
         self._mix_buffers()
         cap = self.cap_frames
         if self.seg is None or self.seg.S != segs.S:
@@ -1833,12 +1894,30 @@ class GpuServer(object):
         now = int(time.time() * 1000)
         seqno = self._seq_order(rx, fa) if self.seq_order else None
         fired = self.fired if tree.watch is not None else None
-        _lib.tree_serve_frames_sessions(
-            tree.tensors, rx, fa.off, fa.length, fa.count, cap, rout, now,
-            fired, seqno, seg_c[0], segs.sessions, segs.wslots, sg.state,
-            sg.bad)
-        L.tree_finish_scan(tree.tensors, fa.count, 0, True, cap,
-                           self.presized[1], self.total_err[0])
+        if ordered:
+            rt = B.decode_requests(rx, fa, out=self.rt)
+            if self.ows is None:
+                self.ows = torch.empty(L.tree_order_workspace(cap), dtype=U8,
+                                       device=tree.device)
+            if defer is None:
+                _lib.tree_serve_ordered_sessions(
+                    tree.tensors, rx, rt.tensors(), fa.count, cap, rout, now,
+                    self.ows, passes, tree.scratch, fired, seqno, seg_c[0],
+                    segs.sessions, segs.wslots, sg.state, sg.bad)
+            else:
+                _lib.tree_serve_ordered_sessions_defer(
+                    tree.tensors, rx, rt.tensors(), fa.count, cap, rout, now,
+                    self.ows, passes, tree.scratch, fired, seqno,
+                    segs.sessions, segs.wslots, sg.state, sg.bad,
+                    self.mix_cls, self.mix_sub, ft.count, sg.f_seg, seg_c,
+                    defer.clipf, defer.deferred)
+        else:
+            _lib.tree_serve_frames_sessions(
+                tree.tensors, rx, fa.off, fa.length, fa.count, cap, rout, now,
+                fired, seqno, seg_c[0], segs.sessions, segs.wslots, sg.state,
+                sg.bad)
+            L.tree_finish_scan(tree.tensors, fa.count, 0, True, cap,
+                               self.presized[1], self.total_err[0])
         if tree.acl is not None:
             _lib.tree_acl_record(tree.acl, rx, fa.off, fa.length, fa.count,
                                  cap, r.opcode, r.err, r.node,
@@ -1848,7 +1927,7 @@ class GpuServer(object):
         a_out, _, a_total, a_err = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=False,
-            total_err=self.total_err, prescanned=True,
+            total_err=self.total_err, prescanned=not ordered,
             rec_off=self.mix_rec_off[0])
         if tree.compact_free:
             tree.free_compact()
@@ -1891,6 +1970,10 @@ class GpuServer(object):
         else:
             _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
                              sg.rep_off)
+        if defer is not None:
+            _lib.order_clip_ranges(defer.clipf, sg.rep_off, rec_off, ft.off,
+                                   segs.starts, ft.count, cap, defer.rep_end,
+                                   defer.used)
         if close:
             self._close_batch(segs, table)
         return self.result
@@ -1924,6 +2007,16 @@ class GpuServer(object):
         L.tree_seq_order(self.tree.tensors, rx, ft.off, ft.length, ft.count,
                          self.cap_frames, self.seq_ws, self.seqno)
         return self.seqno
+
+    def order_counters(self):
+        """The device words :meth:`order_stats` reads — int64 [2]: the
+        largest rank, the scratch bytes asked for (more than the scratch
+        tail holds: a snapshot found no room) — for a caller that folds them
+        into a read of its own (the front end's report); no host read."""
+        if self.ows is None:
+            raise ValueError('order_counters: no ordered serve has run')
+        o = _lib.lib().tree_order_stats_offset(self.cap_frames)
+        return self.ows[o:o + 16].view(torch.int64)
 
     def order_stats(self):
         """(largest same-path rank, scratch bytes used) of the last ordered

@@ -307,6 +307,52 @@ def tree_serve_ordered_sessions(tree, rx, requests, count, ncap, out, now_ms,
                                       wslots, seg_state, bad)
 
 
+def tree_serve_ordered_sessions_defer(tree, rx, requests, count, ncap, out,
+                                      now_ms, ws, passes, scratch, fired,
+                                      seqno, sessions, wslots, seg_state, bad,
+                                      cls, sub, count_all, f_seg_all, seg_c,
+                                      clipf, deferred):
+    """:func:`tree_serve_ordered_sessions` over the serve's class of a session
+    batch of any op mix (``requests`` / ``count``: the class's decoded
+    frames; ``seg_c[0]`` their segments), with deferral in place of the rank
+    refusal (csrc/kernels/tree_order.hip ord_clip_*; the rules:
+    zk_order_clip.h).  Between the ranking and the first serve pass, three
+    launches over the WHOLE batch's tables (``cls`` / ``sub``: the split's,
+    ``count_all``, ``f_seg_all``: :func:`sess_assign`'s, ``seg_c``: the three
+    classes' segment tables): a frame of the serve's class whose rank is >=
+    ``passes``, and every later frame of its segment, gets segment -1 in
+    ``f_seg_all`` and ``seg_c`` — every engine, the catch-up and the close
+    pass refuse it without effect.  ``clipf`` (int64 [S]): the first deferred
+    whole-batch frame of each segment (``ncap``: none); ``deferred`` (int64
+    [1]): the frames deferred.  No host read."""
+    lib().tree_serve_ordered_sessions_defer(
+        tree, rx, requests, count, int(ncap), out, int(now_ms), ws,
+        int(passes), scratch, fired, seqno, sessions, wslots, seg_state, bad,
+        cls, sub, count_all, f_seg_all, list(seg_c), clipf, deferred)
+
+
+def order_clip(rank, passes, cls, sub, count_all, ncap, f_seg_all, seg_c,
+               clipf, deferred):
+    """The deferral stage of :func:`tree_serve_ordered_sessions_defer` alone,
+    over a rank table of the caller's (uint8 [ncap], indexed by the serve
+    class's ``sub``; the low 7 bits are the rank)."""
+    lib().order_clip(rank, int(passes), cls, sub, count_all, int(ncap),
+                     f_seg_all, list(seg_c), clipf, deferred)
+
+
+def order_clip_ranges(clipf, rep_off, rec_off, frame_off, starts, count_all,
+                      ncap, rep_end, used):
+    """After the merge and :func:`sess_ranges` of a batch served with
+    deferral: ``rep_end`` (int64 [S]) — connection s's replies are
+    ``out[rep_off[s]:rep_end[s]]``, the placeholders of its deferred frames
+    lie behind — and ``used`` (int64 [S]), the request bytes of segment s that
+    were consumed (all of them for a segment that was not clipped).
+    ``rec_off``: the merged reply starts; ``frame_off``: the whole batch's
+    frame table.  One launch, no host read."""
+    lib().order_clip_ranges(clipf, rep_off, rec_off, frame_off, starts,
+                            count_all, int(ncap), rep_end, used)
+
+
 def sess_ranges(first, rec_off, count, ncap, total, err, rep_off,
                 slot_first=None, ev_rec_off=None, ev_count=None,
                 ev_bytes=None, ev_err=None, slot_off=None):
@@ -472,7 +518,8 @@ def front_chunk():
     return lib().front_chunk()
 
 
-def front_cut(raw, n, raw_starts, quota, max_packet, take, nfr, flag, fault):
+def front_cut(raw, n, raw_starts, quota, max_packet, take, nfr, flag, fault,
+              mode=0, has_acl=False, nwr=None):
     """The front end's cut (csrc/kernels/front.hip; the rule: zk_front.h
     front_walk), on the current stream: what every connection has received,
     ``raw[:n]`` with ``raw_starts`` (int64 [S + 1]; segment s is
@@ -484,9 +531,23 @@ def front_cut(raw, n, raw_starts, quota, max_packet, take, nfr, flag, fault):
     them; ``flag`` (int32 [S]): 1 where the walk met a length < 0 or >
     ``max_packet`` (nothing at or after it is taken).  ``fault`` (int64
     [1]): 1 when ``raw_starts`` does not begin at 0, descends or passes
-    ``n``; then nothing is taken anywhere.  No host read."""
-    lib().front_cut(raw, int(n), raw_starts, int(quota), int(max_packet),
-                    take, nfr, flag, fault)
+    ``n``; then nothing is taken anywhere.  No host read.
+
+    ``mode=1``: the ordered rule (zk_front.h front_walk_ordered), in front of
+    ``serve_sessions_mixed(ordered=True)``: writes do not end the run.  It is
+    the longest prefix of whole frames, within ``quota``, up to a bad length,
+    in which no CREATE / DELETE / SET_DATA follows a GET_CHILDREN,
+    GET_CHILDREN2, GET_ACL (``has_acl``: the tree keeps an ACL table; without
+    one GET_ACL is of the serve's class) or SET_WATCHES frame, and which a
+    CLOSE_SESSION ends after itself.  ``nwr`` (int32 [S], required): the
+    write frames taken.  ``mode=0`` launches what the call without the
+    keywords does and leaves ``nwr`` alone."""
+    if mode == 0:
+        lib().front_cut(raw, int(n), raw_starts, int(quota), int(max_packet),
+                        take, nfr, flag, fault)
+    else:
+        lib().front_cut(raw, int(n), raw_starts, int(quota), int(max_packet),
+                        take, nfr, flag, fault, int(mode), bool(has_acl), nwr)
 
 
 def front_gather(streams, p_stream, p_src, p_off, P, dst, over):
@@ -504,7 +565,7 @@ def front_gather(streams, p_stream, p_src, p_off, P, dst, over):
 
 
 def front_tx_pieces(rep_off, wslots, resume_off, notif_off, close_off, err,
-                    caps, owner, p_stream, p_src, p_len, stats):
+                    caps, owner, p_stream, p_src, p_len, stats, rep_end=None):
     """The four pieces of every connection's bytes for its socket
     (csrc/kernels/front.hip; the rule: zk_front.h front_piece), on the
     current stream, in sending order: its replies ``rep_off[s]:rep_off[s +
@@ -516,10 +577,12 @@ def front_tx_pieces(rep_off, wslots, resume_off, notif_off, close_off, err,
     (None) or a batch whose ``err`` (int32 [1] or None) is not 0 gives
     empty pieces, and so does a slice outside ``caps`` (the four streams'
     bytes).  ``owner``: int64 [64] workspace.  Piece 4 s + k -> ``p_stream``
-    (int32), ``p_src``, ``p_len`` (int64), each [4 S].  No host read."""
+    (int32), ``p_src``, ``p_len`` (int64), each [4 S].  ``rep_end`` (int64
+    [S] or None): connection s's replies end at ``rep_end[s]`` instead of
+    ``rep_off[s + 1]`` (:func:`order_clip_ranges`).  No host read."""
     lib().front_tx_pieces(rep_off, wslots, resume_off, notif_off, close_off,
                           err, [int(c) for c in caps], owner, p_stream, p_src,
-                          p_len, stats)
+                          p_len, stats, rep_end)
 
 
 def available():

@@ -22,10 +22,31 @@ and frames, and no per-connection or per-frame device read.
 
 Known divergences from ZooKeeper:
 
-* one write per connection per tick: a session batch has no in-batch
-  ordering, so a connection's taken run is any number of reads or exactly one
-  CREATE / DELETE / SET_DATA / CLOSE_SESSION; a pipelined connection's
-  requests still take effect in order, a tick apart;
+* ``order_passes=0`` (the default): one write per connection per tick.  The
+  unordered session batch has no in-batch ordering, so a connection's taken
+  run is any number of reads or exactly one CREATE / DELETE / SET_DATA /
+  CLOSE_SESSION; a pipelined connection's requests still take effect in
+  order, a tick apart;
+* ``order_passes=P``: a connection's pipelined writes are served in one tick,
+  through the ordered session serve of ``P`` passes.  The taken run is cut
+  where the engines' fixed sequence would differ from the connection's own
+  order (no CREATE / DELETE / SET_DATA behind a list, GET_ACL or SET_WATCHES
+  frame of the same run; a CLOSE_SESSION ends it).  A request that more than
+  ``P - 1`` conflicting earlier requests of the tick precede is deferred with
+  everything behind it on its connection and served in a later tick: a path
+  contended by more than ``P`` requests drains ``P`` ranks a tick, in row
+  order, so a low row can delay a high one (no fair rotation).  A deferred
+  SEQUENTIAL create leaves a gap in its parent's cversion, as every refused
+  numbered create does.  The zxids of a tick follow batch order, which is
+  row order, not arrival order.  A read that a later write of the tick
+  overtakes is answered from a snapshot in the tree's scratch tail, and so is
+  a SET_DATA that a later write of the tick overtakes (its reply's Stat).
+  When the tail is full such a request is answered SYSTEMERROR — a read
+  without harm, but such a SET_DATA has been applied: a write that took
+  effect is reported as failed.  ``stats()['order_scratch_full']`` counts the
+  ticks in which that happened; size ``GpuTree(scratch=...)`` for
+  ``cap_frames`` snapshots (a slot is 76 bytes and the node's data, rounded
+  up to 16) and it cannot;
 * inside a tick a connection's replies are sent before its notifications;
 * 64 watcher slots: the 65th live session gets none, its watches arm nothing
   (``stats()['no_watcher_slot']``);
@@ -44,7 +65,8 @@ import numpy as np
 import torch
 
 from .. import consts
-from ..bench.synthetic import (GpuServer, GpuSessionTable, SessionSegments)
+from ..bench.synthetic import (GpuServer, GpuSessionTable, OrderDefer,
+                               SessionSegments)
 from ..ops import _lib
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
@@ -54,6 +76,12 @@ _HS_MAX = 4096                    # a ConnectRequest frame's largest length
 # the report's words behind the per-segment tables
 (_R_FAULT, _R_OVER_RX, _R_OVER_TX, _R_ERR, _R_BAD, _R_DUP, _R_FRAMES,
  _R_CATCHUP, _R_N) = range(9)
+# behind them with order_passes: frames deferred, write frames taken, the
+# largest rank, the snapshot scratch's top
+_R_DEFER, _R_NWR, _R_RANK, _R_SCRATCH, _R_NORD = range(_R_N, _R_N + 5)
+# the flag column with order_passes: bit 0 the cut's flag, bit 1 something of
+# what the cut took was deferred
+_F_BAD, _F_DEFER = 1, 2
 
 
 class _Sess(object):
@@ -109,6 +137,14 @@ class GpuZKServer(object):
     ``table``       a :class:`GpuSessionTable` of one server (default: a new
                     one).
     ``raw_cap``     bytes a tick uploads; also the longest request frame.
+    ``order_passes``  0: a connection's taken run holds one write at most.
+                    ``P >= 1``: the ordered tick (the module's divergence
+                    list) — the ordered cut, ``serve_sessions_mixed(ordered=
+                    True, passes=P, defer=...)``, each connection advanced by
+                    the bytes that were not deferred.  It needs a tree with a
+                    scratch tail (``GpuTree(scratch=...)``; ``ValueError``
+                    without one) and ``cap_frames <= 65536``, and costs
+                    about 3 ``P`` + 8 launches a tick more.
 
     ``.port``, ``.address``, ``.servers()`` and ``.shutdown()`` as
     :class:`FakeZKServer`'s; :meth:`call` runs a function on the server's
@@ -116,7 +152,8 @@ class GpuZKServer(object):
     :meth:`stats` reports the counters."""
 
     def __init__(self, tree, cap_frames, out_cap, max_conns=1024, port=0,
-                 tick_ms=1.0, table=None, host='127.0.0.1', raw_cap=1 << 20):
+                 tick_ms=1.0, table=None, host='127.0.0.1', raw_cap=1 << 20,
+                 order_passes=0):
         if tree.watch is None:
             raise ValueError('GpuZKServer: the tree needs a watch table')
         if table is not None and table.span != 0:
@@ -124,6 +161,18 @@ class GpuZKServer(object):
         if max_conns < 1 or cap_frames < 1 or raw_cap < 4096:
             raise ValueError('GpuZKServer: max_conns, cap_frames >= 1, '
                              'raw_cap >= 4096')
+        self.order_passes = P = int(order_passes)
+        if P < 0 or P > 127:
+            raise ValueError('GpuZKServer: order_passes in 0..127')
+        if P >= 1 and cap_frames > 1 << 16:
+            # (tree_order.hip ORD_MAX_GROUP: a larger group of conflicting
+            # requests is refused wholesale, and deferring all of it every
+            # tick would never drain it)
+            raise ValueError('GpuZKServer: order_passes serves at most 65536 '
+                             'frames a tick')
+        if P >= 1 and tree.scratch is None:
+            raise ValueError('GpuZKServer: order_passes needs a tree with a '
+                             'scratch tail (GpuTree(scratch=...))')
         self.tree = tree
         self.dev = dev = tree.device
         self.cap_frames = int(cap_frames)
@@ -181,7 +230,12 @@ class GpuZKServer(object):
         self.d_tx = torch.zeros(self.tx_cap, dtype=U8, device=dev)
         self.h_tx = _pinned(self.tx_cap, U8, dev)
         self.mv_tx = memoryview(self.h_tx.numpy())
-        self.nrep = 4 * S + 1 + _R_N
+        self.nrep = 4 * S + 1 + (_R_NORD if P else _R_N)
+        # the ordered tick: the cut's write counts, what the serve deferred;
+        # a connection advances by `used`, not by `take`
+        self.d_nwr = torch.zeros(S, dtype=I32, device=dev)
+        self.defer = OrderDefer(S, dev) if P else None
+        self.d_adv = self.defer.used if P else self.d_take
         self.d_report = torch.zeros(self.nrep, dtype=I64, device=dev)
         self.h_report = _pinned(self.nrep, I64, dev)
         self.np_report = self.h_report.numpy()
@@ -199,7 +253,9 @@ class GpuZKServer(object):
              'bad_length', 'no_watcher_slot', 'dup_slot', 'batches_lost',
              'bad_batches', 'catchup_events', 'expiry_passes',
              'sessions_expired', 'sessions_closed', 'handshakes',
-             'host_reads', 'max_reads_per_tick'), 0)
+             'host_reads', 'max_reads_per_tick', 'deferred_frames',
+             'max_writes_per_tick', 'order_max_rank', 'order_scratch_full'),
+            0)
         self._calls = []
         self._lock = threading.Lock()
         self._stop = False
@@ -259,9 +315,17 @@ class GpuZKServer(object):
         connections dropped), ``bad_batches`` (ticks the serve refused:
         ``session_stats()['bad']`` was not 0), ``catchup_events``,
         ``sessions_expired``, ``sessions_closed``, ``max_reads_per_tick``
-        (device-to-host synchronisations of the costliest tick) — and the
-        last batch's ``session_stats``, ``watch_stats``, ``resume_stats``
-        and ``close_stats``, each read once."""
+        (device-to-host synchronisations of the costliest tick); with
+        ``order_passes``: ``deferred_frames`` (frames a tick took and left
+        for a later one; they are not in ``frames``), ``max_writes_per_tick``
+        (write frames the costliest tick's cut took, deferred ones included),
+        ``order_max_rank`` (the longest chain of conflicting requests a tick
+        saw; ``>= order_passes``: it deferred) and ``order_scratch_full``
+        (ticks in which a snapshot found no room in the tree's scratch tail:
+        the request was answered SYSTEMERROR, a SET_DATA among them after it
+        was applied) — and the last batch's
+        ``session_stats``, ``watch_stats``, ``resume_stats`` and
+        ``close_stats``, each read once."""
         def go():
             st = dict(self._stats)
             st['connections'] = sum(1 for c in self.rows if c is not None)
@@ -577,9 +641,11 @@ class GpuZKServer(object):
             self.d_sidx.copy_(self.h_sidx, non_blocking=True)
             self._rows_dirty = False
 
-    def _assemble(self, rep_off, out, err, resume, notif, close):
+    def _assemble(self, rep_off, out, err, resume, notif, close,
+                  rep_end=None):
         """The TX assembly on the device: the pieces, the scan, the gather.
-        ``resume`` / ``notif`` / ``close``: (stream, slot_off) or None."""
+        ``resume`` / ``notif`` / ``close``: (stream, slot_off) or None;
+        ``rep_end``: where the connections' replies end (the ordered tick)."""
         S = self.max_conns
         pairs = (resume, notif, close)
         streams = [out if out is not None else self.d_empty] + \
@@ -588,7 +654,7 @@ class GpuZKServer(object):
         _lib.front_tx_pieces(rep_off, self.d_wslots, offs[0], offs[1],
                              offs[2], err, [int(s.numel()) for s in streams],
                              self.d_owner, self.d_pstream, self.d_psrc,
-                             self.d_plen, self.d_fstats)
+                             self.d_plen, self.d_fstats, rep_end)
         _lib.lib().scan_excl(self.d_plen, self.d_poff, self.d_poff[4 * S:],
                              self.scan_ws)
         _lib.front_gather(streams, self.d_pstream, self.d_psrc, self.d_poff,
@@ -598,7 +664,10 @@ class GpuZKServer(object):
         """The report and ``tx[:total]`` to pinned memory: two reads.
         Returns (report, total)."""
         S = self.max_conns
-        torch.cat([self.d_take, self.d_flag.to(I64),
+        flag = self.d_flag
+        if self.order_passes:
+            flag = flag + (self.d_adv < self.d_take) * _F_DEFER
+        torch.cat([self.d_adv, flag.to(I64),
                    self.table.state.index_select(0, self.d_sidx).to(I64),
                    self.d_poff[0::4]] + words, out=self.d_report)
         self.h_report.copy_(self.d_report, non_blocking=True)
@@ -665,29 +734,52 @@ class GpuZKServer(object):
         self.d_raw[:nup].copy_(self.h_raw[:nup], non_blocking=True)
         self.d_rstarts.copy_(self.h_rstarts, non_blocking=True)
         self._upload_rows()
+        P = self.order_passes
         _lib.front_cut(self.d_raw, nup, self.d_rstarts, quota,
                        consts.MAX_PACKET, self.d_take, self.d_nfr,
-                       self.d_flag, self.d_fault)
+                       self.d_flag, self.d_fault, mode=1 if P else 0,
+                       has_acl=self.tree.acl is not None,
+                       nwr=self.d_nwr if P else None)
         _lib.lib().scan_excl(self.d_take, self.d_starts, self.d_starts[S:],
                              self.scan_ws)
         _lib.front_gather([self.d_raw], None, self.d_rstarts, self.d_starts,
                           S, rx, self.d_over_rx)
-        out, _, err, _ = gs.serve_sessions_mixed(
-            rx, self.d_starts[S:], self.segs, table=self.table, resume=True,
-            close=True)
+        if P:
+            out, _, err, _ = gs.serve_sessions_mixed(
+                rx, self.d_starts[S:], self.segs, table=self.table,
+                resume=True, close=True, ordered=True, passes=P,
+                defer=self.defer)
+        else:
+            out, _, err, _ = gs.serve_sessions_mixed(
+                rx, self.d_starts[S:], self.segs, table=self.table,
+                resume=True, close=True)
         self._assemble(gs.seg.rep_off, out, err,
                        (gs.resume_notif[0], gs.resume_slots[1]),
                        (gs.notif[0], gs.notif_slots[1]),
-                       (gs.close_notif[0], gs.close_slots[1]))
-        rep, total = self._report([
+                       (gs.close_notif[0], gs.close_slots[1]),
+                       self.defer.rep_end if P else None)
+        words = [
             self.d_fault, self.d_over_rx, self.d_over_tx,
             err.reshape(-1)[:1].to(I64), gs.seg.bad[0:1],
             self.d_fstats[0:1], self.d_nfr.sum().reshape(1),
-            gs.resume_counters()[0:1]])
+            gs.resume_counters()[0:1]]
+        if P:
+            words += [self.defer.deferred, self.d_nwr.sum().reshape(1),
+                      gs.order_counters()]
+        rep, total = self._report(words)
         st = self._stats
         st['ticks'] += 1
         words = rep[4 * S + 1:]
         st['frames'] += int(words[_R_FRAMES])
+        if P:
+            st['frames'] -= int(words[_R_DEFER])
+            st['deferred_frames'] += int(words[_R_DEFER])
+            st['max_writes_per_tick'] = max(st['max_writes_per_tick'],
+                                            int(words[_R_NWR]))
+            st['order_max_rank'] = max(st['order_max_rank'],
+                                       int(words[_R_RANK]))
+            if words[_R_SCRATCH] > self.tree.scratch.numel():
+                st['order_scratch_full'] += 1
         st['dup_slot'] += int(words[_R_DUP])
         st['catchup_events'] += int(words[_R_CATCHUP])
         if words[_R_BAD] != 0:
@@ -715,7 +807,9 @@ class GpuZKServer(object):
                 # it): the reply is on its way, then the connection closes
                 st['sessions_closed'] += 1
                 self._end_session(s)
-            elif flag[r] != 0:
+            elif flag[r] & _F_DEFER:
+                pass                                # the rest: the next tick
+            elif flag[r] & _F_BAD:
                 st['bad_length'] += 1
                 self._close_after_send(c)
             elif t == 0:
@@ -745,12 +839,15 @@ class GpuZKServer(object):
         self._upload_rows()
         gs.close_sessions(sids, wsl, table=self.table)
         self.d_take.zero_()
+        if self.order_passes:
+            self.d_adv.zero_()
         self.d_flag.zero_()
         self._assemble(None, None, None, None, None,
                        (gs.close_notif[0], gs.close_slots[1]))
         rep, total = self._report([
             self.d_none, self.d_none, self.d_over_tx, self.d_none,
-            self.d_none, self.d_fstats[0:1], self.d_none, self.d_none])
+            self.d_none, self.d_fstats[0:1], self.d_none, self.d_none] +
+            [self.d_none] * (4 if self.order_passes else 0))
         self._stats['expiry_passes'] += 1
         self._stats['sessions_expired'] += len(due)
         self._deliver(rep, total)
