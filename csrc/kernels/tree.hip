@@ -300,14 +300,8 @@ ZK_DEV int32_t do_create(const ZkTree& t, Lane& L, const uint8_t* data,
 // a request of a segment whose session is not alive SESSION_EXPIRED — both
 // as the ordered passes refuse a request: nothing is looked up, claimed,
 // written, armed or fired.
-struct ServeSegs {
-  const int32_t* f_seg;      // [ncap] frame -> segment
-  const int64_t* sessions;   // [S]
-  const int32_t* wslots;     // [S]
-  const int32_t* seg_state;  // [S] 0 serve, 1 session not alive
-  const int64_t* bad;        // [2] != 0: the table is unsound
-  int64_t S;
-};
+// (the kernels' own name for the launchers' ZkSegs, zk_abi.h)
+struct ServeSegs : ZkSegs {};
 // DEFER (MS only): the ordered serve with deferral (tree_order.hip
 // ord_clip_mark_k).  A deferred frame comes with no segment and the rank byte
 // ORD_RANK: it is refused like any frame of no segment, but the batch is not
@@ -722,7 +716,7 @@ int serve_launch(const ServeLaunch& s, hipStream_t st) {
   if ((o.sizes == nullptr) != (o.block_sums == nullptr)) return -1;
   if (s.tiles != nullptr) {
     // after a rows-deferred scan: the frame table receives the rows
-    if (s.q != nullptr || s.rank != nullptr || s.f_seg != nullptr) return -1;
+    if (s.q != nullptr || s.rank != nullptr || s.segs != nullptr) return -1;
     const auto kt = s.read_only ? tree_serve_tiles_k<true>
                                 : tree_serve_tiles_k<false>;
     kt<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T, 0, st>>>(
@@ -732,13 +726,13 @@ int serve_launch(const ServeLaunch& s, hipStream_t st) {
     return 0;
   }
   const bool parse = s.q == nullptr;
-  if (s.f_seg != nullptr) {
+  if (s.segs != nullptr) {
     // a session batch: the MS instances (none read-only, none over tiles)
-    if (s.read_only || s.sessions == nullptr || s.wslots == nullptr ||
-        s.seg_state == nullptr || s.bad == nullptr || s.nseg < 1)
+    const ServeSegs M{*s.segs};
+    if (s.read_only || M.f_seg == nullptr || M.sessions == nullptr ||
+        M.wslots == nullptr || M.seg_state == nullptr || M.bad == nullptr ||
+        M.S < 1)
       return -1;
-    const ServeSegs M{s.f_seg, s.sessions, s.wslots, s.seg_state, s.bad,
-                      s.nseg};
     if (s.defer) {
       if (parse || s.rank == nullptr) return -1;
       tree_serve_sess_defer_k<<<(unsigned)((s.ncap + TR_T - 1) / TR_T), TR_T,
@@ -806,21 +800,17 @@ int zk_tree_serve_frames(const ZkTree* t, const uint8_t* rx,
 }
 
 // zk_tree_serve_frames for a session batch: session and watcher slot per
-// segment (zk_sess_assign's f_seg / seg_state / bad, the caller's sessions /
-// wslots [nseg]).  No finish, like zk_tree_serve_frames.
+// segment (segs: ZkSegs).  No finish, like zk_tree_serve_frames.
 int zk_tree_serve_frames_sessions(
     const ZkTree* t, const uint8_t* rx, const int64_t* foff,
     const int32_t* flen, const int64_t* n_dev, int64_t ncap,
-    const ZkServeOut* out, int64_t now_ms, int64_t* fired,
-    const int32_t* f_seg, const int64_t* sessions, const int32_t* wslots,
-    const int32_t* seg_state, const int64_t* bad, int64_t nseg,
+    const ZkServeOut* out, int64_t now_ms, int64_t* fired, const ZkSegs* segs,
     hipStream_t st) {
-  if (f_seg == nullptr) return (int)hipErrorInvalidValue;
+  if (segs == nullptr) return (int)hipErrorInvalidValue;
   zk::ServeLaunch s;
   s.tree = t, s.rx = rx, s.foff = foff, s.flen = flen, s.n_dev = n_dev;
   s.ncap = ncap, s.out = out, s.now_ms = now_ms, s.fired = fired;
-  s.f_seg = f_seg, s.sessions = sessions, s.wslots = wslots;
-  s.seg_state = seg_state, s.bad = bad, s.nseg = nseg;
+  s.segs = segs;
   return zk::serve_launch(s, st);
 }
 

@@ -515,19 +515,19 @@ int zk_tree_acl_get(const ZkTree* t, const ZkAclTable* a, const uint8_t* rx,
 // zk_tree_acl_get for the GET_ACL frames of a session batch of any op mix:
 // frame i belongs to segment f_seg[i] (zk_sess_split_segments' table of the
 // GET_ACL class) and is served, or refused as zk_sess.h sess_refusal says
-// (zk_sess_assign's seg_state / bad, nseg segments), header only.
+// (zk_sess_assign's seg_state / bad, S segments), header only.  g: the segment
+// table; its sessions and wslots are not read.
 int zk_tree_acl_get_sessions(const ZkTree* t, const ZkAclTable* a,
                              const uint8_t* rx, const int64_t* foff,
                              const int32_t* flen, const int64_t* n_dev,
-                             int64_t ncap, const int32_t* f_seg,
-                             const int32_t* seg_state, const int64_t* bad,
-                             int64_t nseg, uint8_t* ws, int64_t ws_bytes,
-                             uint8_t* out, int64_t out_cap, int64_t* rec_off,
-                             int64_t* total, int32_t* err, int32_t terminate,
-                             hipStream_t st) {
-  if (f_seg == nullptr || seg_state == nullptr || bad == nullptr || nseg < 1)
+                             int64_t ncap, const ZkSegs* g, uint8_t* ws,
+                             int64_t ws_bytes, uint8_t* out, int64_t out_cap,
+                             int64_t* rec_off, int64_t* total, int32_t* err,
+                             int32_t terminate, hipStream_t st) {
+  if (g == nullptr || g->f_seg == nullptr || g->seg_state == nullptr ||
+      g->bad == nullptr || g->S < 1)
     return -1;
-  const zk::SegTable M{f_seg, nullptr, seg_state, bad, nseg};
+  const zk::SegTable M{g->f_seg, nullptr, g->seg_state, g->bad, g->S};
   return acl_get_launch(t, a, rx, foff, flen, n_dev, ncap, &M, ws, ws_bytes,
                         out, out_cap, rec_off, total, err, terminate, st);
 }

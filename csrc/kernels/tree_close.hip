@@ -309,8 +309,7 @@ int64_t zk_close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap) {
 
 // Pass 1 of a session batch, after its serve and before its reply encode:
 // frames foff / flen (*n_dev of them, at most ncap) of rx[0, rx_len) with
-// zk_sess_assign's f_seg / seg_state / bad and the table's sessions[S] /
-// wslots[S].  Every CLOSE_SESSION frame of a live segment of a sound table
+// the segment table g.  Every CLOSE_SESSION frame of a live segment of a sound table
 // (close_frame) whose reply the serve left UNIMPLEMENTED is answered OK
 // (r_err) and closes its segment; the closing segments' (session, watcher
 // slot), in segment order, become the workspace's list and their number its
@@ -318,11 +317,11 @@ int64_t zk_close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap) {
 // [0] counts the closing frames.
 int zk_close_frames(const ZkTree* t, const uint8_t* rx, int64_t rx_len,
                     const int64_t* foff, const int32_t* flen,
-                    const int64_t* n_dev, int64_t ncap, const int32_t* f_seg,
-                    const int64_t* sessions, const int32_t* wslots,
-                    const int32_t* seg_state, const int64_t* bad, int64_t S,
+                    const int64_t* n_dev, int64_t ncap, const ZkSegs* g,
                     int32_t* r_err, int64_t cap_frames, int64_t node_cap,
                     int64_t* ws, int64_t* stats, hipStream_t st) {
+  if (g == nullptr) return (int)hipErrorInvalidValue;
+  const int64_t S = g->S;
   if (S < 1 || S > 0x7fffffff || ncap < 0 || rx_len < 0 || cap_frames < 0 ||
       node_cap < 0)
     return (int)hipErrorInvalidValue;
@@ -333,15 +332,15 @@ int zk_close_frames(const ZkTree* t, const uint8_t* rx, int64_t rx_len,
     return -4;
   if (ncap > 0) {
     zk::cl_frames_k<<<zk::cl_blocks(ncap), zk::CL_T, 0, st>>>(
-        rx, rx_len, foff, flen, n_dev, ncap, f_seg, seg_state, bad, S, r_err,
-        closing, stats);
+        rx, rx_len, foff, flen, n_dev, ncap, g->f_seg, g->seg_state, g->bad, S,
+        r_err, closing, stats);
     ZK_LAUNCH_CHECK();
   }
   const int rc = zk_scan_excl_i32(closing, ws + w.pos, S, ws + w.tot + zk::CT_K,
                                   ws + w.scan, st);
   if (rc) return rc;
   zk::cl_gather_k<<<zk::cl_blocks(S), zk::CL_T, 0, st>>>(
-      *t, closing, ws + w.pos, sessions, wslots, S, ws + w.sid,
+      *t, closing, ws + w.pos, g->sessions, g->wslots, S, ws + w.sid,
       reinterpret_cast<int32_t*>(ws + w.wslot));
   ZK_LAUNCH_CHECK();
   return 0;

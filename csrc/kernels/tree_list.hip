@@ -403,20 +403,19 @@ int zk_tree_list(const ZkTree* t, const uint8_t* rx, const int64_t* foff,
 // is served for segment f_seg[i] (zk_sess_split_segments' table of the list
 // class) — its watcher slot wslots[seg] arms a watch=1 list's child watch
 // (outside 0..63: none) — or refused as zk_sess.h sess_refusal says
-// (zk_sess_assign's seg_state / bad, nseg segments), header only.
+// (zk_sess_assign's seg_state / bad, S segments), header only.  g: the segment
+// table; its sessions are not read.
 int zk_tree_list_sessions(const ZkTree* t, const uint8_t* rx,
                           const int64_t* foff, const int32_t* flen,
-                          const int64_t* n_dev, int64_t ncap,
-                          const int32_t* f_seg, const int32_t* wslots,
-                          const int32_t* seg_state, const int64_t* bad,
-                          int64_t nseg, int64_t max_frame, int32_t* want,
-                          uint8_t* ws, int64_t ws_bytes, uint8_t* out,
-                          int64_t out_cap, int64_t* rec_off, int64_t* total,
-                          int32_t* err, int32_t terminate, hipStream_t st) {
-  if (f_seg == nullptr || wslots == nullptr || seg_state == nullptr ||
-      bad == nullptr || nseg < 1)
+                          const int64_t* n_dev, int64_t ncap, const ZkSegs* g,
+                          int64_t max_frame, int32_t* want, uint8_t* ws,
+                          int64_t ws_bytes, uint8_t* out, int64_t out_cap,
+                          int64_t* rec_off, int64_t* total, int32_t* err,
+                          int32_t terminate, hipStream_t st) {
+  if (g == nullptr || g->f_seg == nullptr || g->wslots == nullptr ||
+      g->seg_state == nullptr || g->bad == nullptr || g->S < 1)
     return -1;
-  const zk::SegTable M{f_seg, wslots, seg_state, bad, nseg};
+  const zk::SegTable M{g->f_seg, g->wslots, g->seg_state, g->bad, g->S};
   return list_launch(t, rx, foff, flen, n_dev, ncap, -1, &M, max_frame, want,
                      ws, ws_bytes, out, out_cap, rec_off, total, err,
                      terminate, st);

@@ -235,17 +235,8 @@ __global__ __launch_bounds__(TR_T) void ord_rank_k(int64_t ncap, OrderWs w,
 // surviving frame has a rank >= passes.  All tables here are the WHOLE
 // batch's (cls / sub: the split's; f_seg: the assign's), nall its device
 // frame count; every index is checked against ncap and S.
-struct OrdClip {
-  const int32_t* cls;      // [ncap] the split's class per frame
-  const int32_t* sub;      // [ncap] its index in the class's table
-  const int64_t* nall;     // the whole batch's frame count
-  int32_t* f_seg;          // [ncap] frame -> segment (deferred: -1)
-  int32_t* seg_c[3];       // [ncap] each class's frame -> segment
-  int64_t* clipf;          // [S] first deferred frame (ncap: none)
-  int64_t* deferred;       // [1] frames deferred
-  const int64_t* bad;      // the table's fault word (or null): != 0, the batch
-  int64_t S;               // is refused as a whole and nothing is deferred
-};
+// (the kernels' own name for the launchers' ZkOrdClip, zk_abi.h)
+struct OrdClip : ZkOrdClip {};
 
 __global__ __launch_bounds__(TR_T) void ord_clip_init_k(OrdClip c,
                                                         int64_t ncap) {
@@ -330,8 +321,9 @@ __global__ __launch_bounds__(TR_T) void ord_clip_ranges_k(
 static_assert(CLIP_RANK == ORD_RANK, "zk_order_clip.h: the rank bits");
 
 // mark_rank: the rank table is the ordered serve's own (not a caller's).
-int clip_launch(const OrdClip& c, uint8_t* rank, int64_t ncap,
+int clip_launch(const ZkOrdClip& clip, uint8_t* rank, int64_t ncap,
                 int32_t passes, bool mark_rank, hipStream_t st) {
+  const OrdClip c{clip};
   if (ncap < 1 || ncap > 0x7fffffff || c.S < 1 || c.S > 0x7fffffff ||
       passes < 1)
     return -1;
@@ -396,6 +388,15 @@ static int64_t order_layout(int64_t ncap, uint8_t* ws, zk::OrderWs* w,
   return o;
 }
 
+// A deferral's tables: every one of them given, at least one segment.
+static bool clip_ok(const ZkOrdClip* c) {
+  return c != nullptr && c->cls != nullptr && c->sub != nullptr &&
+         c->nall != nullptr && c->f_seg != nullptr &&
+         c->seg_c[0] != nullptr && c->seg_c[1] != nullptr &&
+         c->seg_c[2] != nullptr && c->clipf != nullptr &&
+         c->deferred != nullptr && c->S >= 1;
+}
+
 // Bytes of the ordering workspace for up to ncap requests.
 int64_t zk_tree_order_workspace(int64_t ncap) {
   return order_layout(ncap, nullptr, nullptr, nullptr, nullptr);
@@ -408,16 +409,16 @@ int64_t zk_tree_order_workspace(int64_t ncap) {
 // answered SYSTEMERROR and shows in the max rank (zk_tree_order_stats_offset;
 // the caller can read it and use more passes).  The launches do not depend
 // on the ranks: no host read.
-// (segs: a session batch's table, ServeLaunch's f_seg .. nseg; null: one
-// session, one watcher slot)
+// (segs: a session batch's table; null: one session, one watcher slot.  clip,
+// with segs: deferral in place of the rank refusal, see below)
 static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
                          const int64_t* n_dev, int64_t ncap,
                          const ZkServeOut* out, int64_t session,
                          int64_t now_ms, uint8_t* ws, int64_t ws_bytes,
                          int32_t passes, int64_t snap_base, int64_t snap_cap,
                          int32_t wslot, int64_t* fired,
-                         const zk::ServeLaunch* segs, hipStream_t st,
-                         const zk::OrdClip* clip = nullptr) {
+                         const ZkSegs* segs, const ZkOrdClip* clip,
+                         hipStream_t st) {
   if (ncap <= 0) return 0;
   if (ncap > zk::ORD_FM) return -1;          // packed group counts
   if (passes < 1 || passes > zk::ORD_RANK) return -1;
@@ -457,12 +458,7 @@ static int ordered_serve(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
   s.out = out, s.session = session, s.now_ms = now_ms, s.rank = rank;
   s.snap_base = snap_base, s.snap_cap = snap_cap, s.snap_top = &w.ctr[2];
   s.wslot = wslot, s.fired = fired;
-  if (segs != nullptr) {
-    s.f_seg = segs->f_seg, s.sessions = segs->sessions;
-    s.wslots = segs->wslots, s.seg_state = segs->seg_state;
-    s.bad = segs->bad, s.nseg = segs->nseg;
-    s.defer = clip != nullptr;
-  }
+  s.segs = segs, s.defer = clip != nullptr;
   for (s.pass = 0; s.pass < passes; ++s.pass) {
     const int32_t last = s.pass == passes - 1;
     s.last_pass = last;
@@ -484,77 +480,40 @@ int zk_tree_serve_ordered(const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
                           int32_t wslot, int64_t* fired, hipStream_t st) {
   return ordered_serve(t, rx, q, n_dev, ncap, out, session, now_ms, ws,
                        ws_bytes, passes, snap_base, snap_cap, wslot, fired,
-                       nullptr, st);
+                       nullptr, nullptr, st);
 }
 
-// zk_tree_serve_ordered for a session batch (zk_tree_serve_frames_sessions'
-// table): requests on one path are applied in stream order whichever
-// segments they come from.
+// zk_tree_serve_ordered for a session batch (segs: ZkSegs): requests on one
+// path are applied in stream order whichever segments they come from.
+// clip (or null): over the serve's class of a session batch of any op mix,
+// deferral in place of the rank refusal (ord_clip_* above; the rules:
+// zk_order_clip.h).  (rx .. segs) are then the class's compacted frames —
+// segs->f_seg is clip->seg_c[0] — and clip the WHOLE batch's tables.  Three
+// launches between the ranking and the first pass; no host read.
 int zk_tree_serve_ordered_sessions(
     const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
     const int64_t* n_dev, int64_t ncap, const ZkServeOut* out, int64_t now_ms,
     uint8_t* ws, int64_t ws_bytes, int32_t passes, int64_t snap_base,
-    int64_t snap_cap, int64_t* fired, const int32_t* f_seg,
-    const int64_t* sessions, const int32_t* wslots, const int32_t* seg_state,
-    const int64_t* bad, int64_t nseg, hipStream_t st) {
-  if (f_seg == nullptr) return (int)hipErrorInvalidValue;
-  zk::ServeLaunch m;
-  m.f_seg = f_seg, m.sessions = sessions, m.wslots = wslots;
-  m.seg_state = seg_state, m.bad = bad, m.nseg = nseg;
-  return ordered_serve(t, rx, q, n_dev, ncap, out, 0, now_ms, ws, ws_bytes,
-                       passes, snap_base, snap_cap, -1, fired, &m, st);
-}
-
-// zk_tree_serve_ordered_sessions for the serve's class of a session batch of
-// any op mix, with deferral in place of the rank refusal (ord_clip_* above;
-// the rules: zk_order_clip.h).  (rx .. nseg) as there, over the class's
-// compacted frames: f_seg is seg_c0.  Then the WHOLE batch's tables: the
-// split's cls / sub [ncap], its frame count nall, the assign's f_seg_all
-// [ncap] and the three classes' segment tables -> the deferred frames'
-// entries of f_seg_all / seg_c* become -1, clipf[nseg] (per segment the first
-// deferred whole-batch frame; ncap: none) and deferred[1] (frames deferred).
-// Three launches between the ranking and the first pass; no host read.
-int zk_tree_serve_ordered_sessions_defer(
-    const ZkTree* t, const uint8_t* rx, const ZkReqOut* q,
-    const int64_t* n_dev, int64_t ncap, const ZkServeOut* out, int64_t now_ms,
-    uint8_t* ws, int64_t ws_bytes, int32_t passes, int64_t snap_base,
-    int64_t snap_cap, int64_t* fired, const int64_t* sessions,
-    const int32_t* wslots, const int32_t* seg_state, const int64_t* bad,
-    int64_t nseg, const int32_t* cls, const int32_t* sub, const int64_t* nall,
-    int32_t* f_seg_all, int32_t* seg_c0, int32_t* seg_c1, int32_t* seg_c2,
-    int64_t* clipf, int64_t* deferred, hipStream_t st) {
-  if (seg_c0 == nullptr || seg_c1 == nullptr || seg_c2 == nullptr ||
-      cls == nullptr || sub == nullptr || nall == nullptr ||
-      f_seg_all == nullptr || clipf == nullptr || deferred == nullptr ||
-      nseg < 1)
+    int64_t snap_cap, int64_t* fired, const ZkSegs* segs,
+    const ZkOrdClip* clip, hipStream_t st) {
+  if (segs == nullptr || segs->f_seg == nullptr ||
+      (clip != nullptr &&
+       (!clip_ok(clip) || clip->seg_c[0] != segs->f_seg ||
+        clip->S != segs->S || clip->bad != segs->bad)))
     return (int)hipErrorInvalidValue;
-  zk::ServeLaunch m;
-  m.f_seg = seg_c0, m.sessions = sessions, m.wslots = wslots;
-  m.seg_state = seg_state, m.bad = bad, m.nseg = nseg;
-  zk::OrdClip c;
-  c.cls = cls, c.sub = sub, c.nall = nall, c.f_seg = f_seg_all;
-  c.seg_c[0] = seg_c0, c.seg_c[1] = seg_c1, c.seg_c[2] = seg_c2;
-  c.clipf = clipf, c.deferred = deferred, c.S = nseg, c.bad = bad;
   return ordered_serve(t, rx, q, n_dev, ncap, out, 0, now_ms, ws, ws_bytes,
-                       passes, snap_base, snap_cap, -1, fired, &m, st, &c);
+                       passes, snap_base, snap_cap, -1, fired, segs, clip, st);
 }
 
 // The deferral stage alone (the three launches), over a rank table of the
-// caller's: rank[ncap], the rest as zk_tree_serve_ordered_sessions_defer.
-int zk_order_clip(const uint8_t* rank, int32_t passes, const int32_t* cls,
-                  const int32_t* sub, const int64_t* nall, int64_t ncap,
-                  int32_t* f_seg_all, int32_t* seg_c0, int32_t* seg_c1,
-                  int32_t* seg_c2, int64_t* clipf, int64_t* deferred,
-                  int64_t nseg, hipStream_t st) {
-  if (rank == nullptr || nseg < 1 || ncap < 1)
+// caller's: rank[ncap] and the tables (bad null).
+int zk_order_clip(const uint8_t* rank, int32_t passes, const ZkOrdClip* clip,
+                  int64_t ncap, hipStream_t st) {
+  if (rank == nullptr || !clip_ok(clip) || clip->bad != nullptr || ncap < 1)
     return (int)hipErrorInvalidValue;
-  zk::OrdClip c;
-  c.cls = cls, c.sub = sub, c.nall = nall, c.f_seg = f_seg_all;
-  c.seg_c[0] = seg_c0, c.seg_c[1] = seg_c1, c.seg_c[2] = seg_c2;
-  c.clipf = clipf, c.deferred = deferred, c.S = nseg, c.bad = nullptr;
   // (the caller's rank table is only read)
-  return zk::clip_launch(c, const_cast<uint8_t*>(rank), ncap, passes, false,
-                         st);
+  return zk::clip_launch(*clip, const_cast<uint8_t*>(rank), ncap, passes,
+                         false, st);
 }
 
 // After the merge and zk_sess_ranges: per segment where its replies end and

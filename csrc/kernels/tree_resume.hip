@@ -269,8 +269,8 @@ int64_t zk_watch_resume_sessions_workspace(int64_t ncap, int64_t ecap) {
 }
 
 // The catch-up of a session batch after its serve: frames foff / flen
-// (*n_dev of them, at most ncap) of rx[0, rx_len) with zk_sess_assign's f_seg
-// / seg_state / bad and the table's wslots[S].  -> the events, ecap records of
+// (*n_dev of them, at most ncap) of rx[0, rx_len) with the segment table g
+// (its sessions are not read).  -> the events, ecap records of
 // room, in stream order (ev_*; ev_total[0] written, [1] all), the same
 // grouped by watcher slot (g_*, slot_first[65]: zk_sess_group_events), and
 // stats[8]: events, events written, watches re-armed, paths listed, paths
@@ -279,14 +279,14 @@ int64_t zk_watch_resume_sessions_workspace(int64_t ncap, int64_t ecap) {
 // its 4 length bytes.
 int zk_watch_resume_sessions(
     const ZkTree* t, const uint8_t* rx, int64_t rx_len, const int64_t* foff,
-    const int32_t* flen, const int64_t* n_dev, int64_t ncap,
-    const int32_t* f_seg, const int32_t* wslots, const int32_t* seg_state,
-    const int64_t* bad, int64_t S, int64_t* ws, int64_t ecap,
-    int32_t* ev_slot, int32_t* ev_type, int64_t* ev_poff, int32_t* ev_plen,
-    int64_t* ev_total, int32_t* g_slot, int32_t* g_type, int64_t* g_poff,
-    int32_t* g_plen, int64_t* slot_first, int64_t* stats, hipStream_t st) {
+    const int32_t* flen, const int64_t* n_dev, int64_t ncap, const ZkSegs* g,
+    int64_t* ws, int64_t ecap, int32_t* ev_slot, int32_t* ev_type,
+    int64_t* ev_poff, int32_t* ev_plen, int64_t* ev_total, int32_t* g_slot,
+    int32_t* g_type, int64_t* g_poff, int32_t* g_plen, int64_t* slot_first,
+    int64_t* stats, hipStream_t st) {
   if (t->wt_key == nullptr) return -1;
-  if (ncap < 1 || ncap > 0x7fffffff || ecap < 1 || S < 1 || rx_len < 0)
+  if (ncap < 1 || ncap > 0x7fffffff || ecap < 1 || g == nullptr || g->S < 1 ||
+      rx_len < 0)
     return (int)hipErrorInvalidValue;
   const zk::RsWork w = zk::rs_work(ncap, ecap);
   int64_t* cnt = ws + w.cnt;
@@ -298,7 +298,8 @@ int zk_watch_resume_sessions(
   int32_t* flag = reinterpret_cast<int32_t*>(ws + w.flag);
   int32_t* edec = reinterpret_cast<int32_t*>(ws + w.edec);
   const zk::RsBatch b{rx, rx_len, (int64_t)((uintptr_t)rx & 15), foff, flen,
-                      n_dev, ncap, f_seg, wslots, seg_state, bad, S};
+                      n_dev, ncap, g->f_seg, g->wslots, g->seg_state,
+                      g->bad, g->S};
   if (hipMemsetAsync(stats, 0, zk::RST_N * sizeof(int64_t), st) != hipSuccess)
     return -4;
   zk::rs_list_k<false><<<(unsigned)ncap, zk::RS_T, 0, st>>>(

@@ -108,6 +108,38 @@ struct ZkServeOut {
   int64_t *slot, *sizes, *block_sums;
 };
 
+// The segment table of a session batch (tree_sess.hip; the rule: zk_sess.h):
+// zk_sess_assign's f_seg / seg_state / bad and the caller's sessions / wslots.
+// Every engine of a session batch takes it in place of one session and one
+// watcher slot; the list, GET_ACL and catch-up engines read no sessions, the
+// GET_ACL engine no wslots.
+struct ZkSegs {
+  const int32_t* f_seg;      // [ncap] frame -> segment (of the whole batch,
+                             // or of one class: zk_sess_split_segments)
+  const int64_t* sessions;   // [S]
+  const int32_t* wslots;     // [S]
+  const int32_t* seg_state;  // [S] 0 serve, 1 session not alive
+  const int64_t* bad;        // [2] != 0: the table is unsound
+  int64_t S;
+};
+
+// Deferral in the ordered session serve (tree_order.hip ord_clip_*; the rules:
+// zk_order_clip.h), over the WHOLE batch of any op mix: the split's cls / sub,
+// its frame count, the assign's f_seg and the three classes' segment tables ->
+// the deferred frames' entries of f_seg / seg_c become -1, clipf[S] (per
+// segment the first deferred whole-batch frame; ncap: none), deferred[1].
+struct ZkOrdClip {
+  const int32_t* cls;      // [ncap] the split's class per frame
+  const int32_t* sub;      // [ncap] its index in the class's table
+  const int64_t* nall;     // the whole batch's frame count
+  int32_t* f_seg;          // [ncap] frame -> segment (deferred: -1)
+  int32_t* seg_c[3];       // [ncap] each class's frame -> segment
+  int64_t* clipf;          // [S] first deferred frame (ncap: none)
+  int64_t* deferred;       // [1] frames deferred
+  const int64_t* bad;      // the table's fault word (or null): != 0, the batch
+  int64_t S;               // is refused as a whole and nothing is deferred
+};
+
 // The GPU-resident synthetic server's tree (zk_tree.h; kernels in tree.hip
 // and tree_{order,seq,list,watch}.hip).
 struct ZkTree {
@@ -450,8 +482,10 @@ int zk_scan_small_i64(const int64_t*, int64_t*, int64_t, int64_t*,
 // Session batches (tree_sess.hip; the rule: zk_sess.h).  zk_sess_assign:
 // (frames off / len, count, ncap, starts[S + 1], sessions[S], S, the session
 // table or null, its server id) -> f_seg[ncap], first[S + 1], seg_state[S],
-// bad[2].  The serves take (..., fired, f_seg, sessions, wslots, seg_state,
-// bad, S) in place of one session and one watcher slot.  zk_sess_ranges:
+// bad[2].  The serves take (..., fired, the segment table: ZkSegs) in place
+// of one session and one watcher slot; the ordered one also the deferral's
+// tables (ZkOrdClip; its seg_c[0] is then the table's f_seg) or null: a rank
+// the passes cannot reach is refused.  zk_sess_ranges:
 // (first, S, the reply encode's rec_off / count / ncap / total / err) ->
 // rep_off[S + 1], and with slot_first (the grouped notification encode's
 // rec_off / count / ecap / total / err) slot_off[65].  zk_sess_group_events:
@@ -464,17 +498,14 @@ int zk_sess_assign(const int64_t*, const int32_t*, const int64_t*, int64_t,
 int zk_tree_serve_frames_sessions(const ZkTree*, const uint8_t*,
                                   const int64_t*, const int32_t*,
                                   const int64_t*, int64_t, const ZkServeOut*,
-                                  int64_t, int64_t*, const int32_t*,
-                                  const int64_t*, const int32_t*,
-                                  const int32_t*, const int64_t*, int64_t,
+                                  int64_t, int64_t*, const ZkSegs*,
                                   hipStream_t);
 int zk_tree_serve_ordered_sessions(const ZkTree*, const uint8_t*,
                                    const ZkReqOut*, const int64_t*, int64_t,
                                    const ZkServeOut*, int64_t, uint8_t*,
                                    int64_t, int32_t, int64_t, int64_t,
-                                   int64_t*, const int32_t*, const int64_t*,
-                                   const int32_t*, const int32_t*,
-                                   const int64_t*, int64_t, hipStream_t);
+                                   int64_t*, const ZkSegs*, const ZkOrdClip*,
+                                   hipStream_t);
 int zk_sess_ranges(const int64_t*, int64_t, const int64_t*, const int64_t*,
                    int64_t, const int64_t*, const int32_t*, int64_t*,
                    const int64_t*, const int64_t*, const int64_t*, int64_t,
@@ -487,55 +518,51 @@ int zk_sess_group_events(const int32_t*, const int32_t*, const int64_t*,
 // Session batches of any op mix.  zk_sess_split_segments: (f_seg, the
 // split's cls / sub, count, ncap) -> f_seg_c0 / c1 / c2 [ncap], each class's
 // frame -> segment.  zk_tree_list_sessions / zk_tree_acl_get_sessions:
-// zk_tree_list / zk_tree_acl_get with (the class's f_seg, wslots — the list
-// only —, seg_state, bad, S) after ncap, in place of the watcher slot.
+// zk_tree_list / zk_tree_acl_get with the segment table (ZkSegs; f_seg: the
+// class's) after ncap, in place of the watcher slot.
 int zk_sess_split_segments(const int32_t*, const int32_t*, const int32_t*,
                            const int64_t*, int64_t, int32_t*, int32_t*,
                            int32_t*, hipStream_t);
 int zk_tree_list_sessions(const ZkTree*, const uint8_t*, const int64_t*,
                           const int32_t*, const int64_t*, int64_t,
-                          const int32_t*, const int32_t*, const int32_t*,
-                          const int64_t*, int64_t, int64_t, int32_t*,
+                          const ZkSegs*, int64_t, int32_t*,
                           uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
                           int64_t*, int32_t*, int32_t, hipStream_t);
 int zk_tree_acl_get_sessions(const ZkTree*, const ZkAclTable*,
                              const uint8_t*, const int64_t*, const int32_t*,
-                             const int64_t*, int64_t, const int32_t*,
-                             const int32_t*, const int64_t*, int64_t,
+                             const int64_t*, int64_t, const ZkSegs*,
                              uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
                              int64_t*, int32_t*, int32_t, hipStream_t);
 // The SET_WATCHES catch-up of a session batch (tree_resume.hip; the rules:
 // zk_resume.h), after its serve: (tree, rx, its length, frames off / len,
-// count, ncap, f_seg, wslots, seg_state, bad, S, workspace, ecap) -> the
+// count, ncap, the segment table, workspace, ecap) -> the
 // events in stream order (ev_slot / type / poff / plen [ecap], ev_total[2]),
 // grouped by watcher slot (g_* [ecap], slot_first[65]) and stats[8].  The
 // workspace: int64 words for (ncap, ecap).
 int64_t zk_watch_resume_sessions_workspace(int64_t ncap, int64_t ecap);
 int zk_watch_resume_sessions(const ZkTree*, const uint8_t*, int64_t,
                              const int64_t*, const int32_t*, const int64_t*,
-                             int64_t, const int32_t*, const int32_t*,
-                             const int32_t*, const int64_t*, int64_t,
-                             int64_t*, int64_t, int32_t*, int32_t*, int64_t*,
-                             int32_t*, int64_t*, int32_t*, int32_t*, int64_t*,
-                             int32_t*, int64_t*, int64_t*, hipStream_t);
+                             int64_t, const ZkSegs*, int64_t*, int64_t,
+                             int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
+                             int32_t*, int32_t*, int64_t*, int32_t*, int64_t*,
+                             int64_t*, hipStream_t);
 // Close / expire many sessions in one pass (tree_close.hip; the rules:
 // zk_close.h).  zk_close_workspace: int64 words for (frames a batch, sessions
 // a list, the tree's node slots); its head is the fired watches' record area
 // (zk_tree_expire's rec, cap_frames records).  zk_close_frames, between a
 // session batch's serve and its reply encode: (tree, rx, its length, frames
-// off / len, count, ncap, f_seg, sessions, wslots, seg_state, bad, S, the
-// serve's r_err, cap_frames, node slots, workspace) -> every CLOSE_SESSION
-// frame of a live segment answered OK, the closing segments' list and count
-// in the workspace, stats[8].  zk_close_sessions: (tree, sids[K], wslots[K]
+// off / len, count, ncap, the segment table, the serve's r_err, cap_frames,
+// node slots, workspace) -> every CLOSE_SESSION frame of a live segment
+// answered OK, the closing segments' list and count in the workspace,
+// stats[8].  zk_close_sessions: (tree, sids[K], wslots[K]
 // or null, K, S, cap_frames, node slots, the session table or null, its
 // server id, workspace) -> removed[S] (+= per listed session), stats[8];
 // sids null: the list zk_close_frames left.
 int64_t zk_close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap);
 int zk_close_frames(const ZkTree*, const uint8_t*, int64_t, const int64_t*,
-                    const int32_t*, const int64_t*, int64_t, const int32_t*,
-                    const int64_t*, const int32_t*, const int32_t*,
-                    const int64_t*, int64_t, int32_t*, int64_t, int64_t,
-                    int64_t*, int64_t*, hipStream_t);
+                    const int32_t*, const int64_t*, int64_t, const ZkSegs*,
+                    int32_t*, int64_t, int64_t, int64_t*, int64_t*,
+                    hipStream_t);
 int zk_close_sessions(const ZkTree*, const int64_t*, const int32_t*, int64_t,
                       int64_t, int64_t, int64_t, const ZkSessionTable*,
                       int64_t, int64_t*, unsigned long long*, int64_t*,
@@ -570,24 +597,13 @@ int zk_front_tx_pieces_end(const int64_t*, const int64_t*, const int32_t*,
                            const int64_t* const*, const int32_t*,
                            const int64_t*, int64_t, int64_t*, int32_t*,
                            int64_t*, int64_t*, int64_t*, hipStream_t);
-// Deferral in the ordered session serve (tree_order.hip ord_clip_*; the rules:
-// zk_order_clip.h).  zk_tree_serve_ordered_sessions_defer:
-// zk_tree_serve_ordered_sessions over the serve's class of a batch of any op
-// mix (f_seg is seg_c0 below), then the whole batch's (cls, sub, count,
-// f_seg, seg_c0 / c1 / c2) and clipf[S], deferred[1].  zk_order_clip: the
-// stage alone over (rank[ncap], passes, cls, sub, count, ncap, f_seg, seg_c0 /
-// c1 / c2, clipf, deferred, S).  zk_order_clip_ranges: (clipf, rep_off[S + 1],
-// the merged rec_off, the frames' off, starts[S + 1], count, ncap, S) ->
+// Deferral in the ordered session serve (ZkOrdClip above) apart from the
+// serve.  zk_order_clip: the stage alone over (rank[ncap], passes, the tables
+// — bad null —, ncap).  zk_order_clip_ranges: (clipf, rep_off[S + 1], the
+// merged rec_off, the frames' off, starts[S + 1], count, ncap, S) ->
 // rep_end[S], used[S].
-int zk_tree_serve_ordered_sessions_defer(
-    const ZkTree*, const uint8_t*, const ZkReqOut*, const int64_t*, int64_t,
-    const ZkServeOut*, int64_t, uint8_t*, int64_t, int32_t, int64_t, int64_t,
-    int64_t*, const int64_t*, const int32_t*, const int32_t*, const int64_t*,
-    int64_t, const int32_t*, const int32_t*, const int64_t*, int32_t*,
-    int32_t*, int32_t*, int32_t*, int64_t*, int64_t*, hipStream_t);
-int zk_order_clip(const uint8_t*, int32_t, const int32_t*, const int32_t*,
-                  const int64_t*, int64_t, int32_t*, int32_t*, int32_t*,
-                  int32_t*, int64_t*, int64_t*, int64_t, hipStream_t);
+int zk_order_clip(const uint8_t*, int32_t, const ZkOrdClip*, int64_t,
+                  hipStream_t);
 int zk_order_clip_ranges(const int64_t*, const int64_t*, const int64_t*,
                          const int64_t*, const int64_t*, const int64_t*,
                          int64_t, int64_t, int64_t*, int64_t*, hipStream_t);
@@ -601,6 +617,8 @@ static_assert(sizeof(ZkRespBatch) == 10 * 8, "ZkRespBatch layout");
 static_assert(sizeof(ZkReplyOut) == 12 * 8, "ZkReplyOut layout");
 static_assert(sizeof(ZkReqOut) == 12 * 8, "ZkReqOut layout");
 static_assert(sizeof(ZkServeOut) == 10 * 8, "ZkServeOut layout");
+static_assert(sizeof(ZkSegs) == 6 * 8, "ZkSegs layout");
+static_assert(sizeof(ZkOrdClip) == 11 * 8, "ZkOrdClip layout");
 static_assert(sizeof(ZkSessionTable) == 7 * 8, "ZkSessionTable layout");
 static_assert(sizeof(ZkAclTable) == 8 * 8, "ZkAclTable layout");
 static_assert(offsetof(ZkAclTable, arena) == 2 * 8, "ZkAclTable.arena");

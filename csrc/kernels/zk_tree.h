@@ -889,16 +889,9 @@ struct ServeLaunch {
   const ZkFrameTiles* tiles = nullptr;
   int64_t* rows_off = nullptr;
   int32_t* rows_len = nullptr;
-  // a session batch (tree_sess.hip; f_seg set picks the serve's MS
-  // instances): frame -> segment, and per segment (nseg of them) the
-  // session, the watcher slot and the state; bad[0] != 0 refuses the batch.
-  // session / wslot above are then unused
-  const int32_t* f_seg = nullptr;
-  const int64_t* sessions = nullptr;
-  const int32_t* wslots = nullptr;
-  const int32_t* seg_state = nullptr;
-  const int64_t* bad = nullptr;
-  int64_t nseg = 0;
+  // a session batch (tree_sess.hip; set, it picks the serve's MS instances):
+  // the segment table.  session / wslot above are then unused
+  const ZkSegs* segs = nullptr;
   // the ordered passes of a session batch served with deferral (q and rank
   // set): the MS instance that keeps a deferred SEQUENTIAL create's number
   int32_t defer = 0;

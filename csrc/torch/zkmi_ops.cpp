@@ -243,6 +243,88 @@ ZkServeOut serve_out(const std::vector<Tensor>& r, int64_t ncap,
   return o;
 }
 
+// The segment table of a session batch (csrc/kernels/tree_sess.hip):
+// [f_seg, sessions, wslots, seg_state, bad]; f_seg [ncap] (the whole batch's or
+// one class's), sessions and wslots [S], seg_state [>= S], bad [2].
+ZkSegs segs(const std::vector<Tensor>& v, int64_t ncap, const Tensor* dev) {
+  need(v, 5, "segment table");
+  ZkSegs m;
+  m.S = v[1].numel();
+  TORCH_CHECK(m.S >= 1 && m.S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  m.f_seg = P<int32_t>(v[0], I32, ncap, "f_seg", dev);
+  m.sessions = P<int64_t>(v[1], I64, m.S, "sessions", dev);
+  m.wslots = P<int32_t>(v[2], I32, m.S, "wslots", dev);
+  TORCH_CHECK(v[2].numel() == m.S, "zkmi: wslots has ", v[2].numel(),
+              " entries, sessions ", m.S);
+  m.seg_state = P<int32_t>(v[3], I32, m.S, "seg_state", dev);
+  m.bad = P<int64_t>(v[4], I64, 2, "bad", dev);
+  return m;
+}
+
+// The deferral's tables (zk_order_clip.h): [cls, sub, count_all, f_seg_all,
+// seg_c0, seg_c1, seg_c2, clipf, deferred], all but the last two of the whole
+// batch.  m: the table of the serve they go with (seg_c0 is its f_seg), or
+// null: the stage alone, clipf's length gives S.
+ZkOrdClip ord_clip(const std::vector<Tensor>& v, int64_t ncap, const ZkSegs* m,
+                   const Tensor* dev) {
+  need(v, 9, "clip tables");
+  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1, "zkmi: order_clip ncap");
+  ZkOrdClip c;
+  c.S = m != nullptr ? m->S : v[7].numel();
+  TORCH_CHECK(c.S >= 1 && c.S < (1ll << 31) - 1,
+              "zkmi: a segment table has at least one segment");
+  c.bad = m != nullptr ? m->bad : nullptr;
+  c.cls = P<int32_t>(v[0], I32, ncap, "cls", dev);
+  c.sub = P<int32_t>(v[1], I32, ncap, "sub", dev);
+  c.nall = P<int64_t>(v[2], I64, 1, "count_all", dev);
+  c.f_seg = P<int32_t>(v[3], I32, ncap, "f_seg_all", dev);
+  c.seg_c[0] = P<int32_t>(v[4], I32, ncap, "seg_c[0]", dev);
+  c.seg_c[1] = P<int32_t>(v[5], I32, ncap, "seg_c[1]", dev);
+  c.seg_c[2] = P<int32_t>(v[6], I32, ncap, "seg_c[2]", dev);
+  c.clipf = P<int64_t>(v[7], I64, c.S, "clipf", dev);
+  c.deferred = P<int64_t>(v[8], I64, 1, "deferred", dev);
+  TORCH_CHECK(m == nullptr || c.seg_c[0] == m->f_seg,
+              "zkmi: the clip's seg_c[0] must be the segment table's f_seg");
+  return c;
+}
+
+// What the ordered serves share: the passes, the order workspace and, when
+// `scratch` is given, where snapshot replies go.  scratch is the slab's tail
+// past the tree's view of it (t[6] = slab[:cap]); the replies are named by
+// their offset from the slab start, so the encoder must be given the whole
+// slab.
+struct OrdArgs {
+  uint8_t* ws;
+  int64_t ws_bytes;
+  int32_t passes;
+  int64_t snap_base = 0, snap_cap = 0;
+};
+
+OrdArgs ord_args(const std::vector<Tensor>& t, const ZkTree& s, int64_t ncap,
+                 const Tensor& ws, int64_t passes,
+                 const c10::optional<Tensor>& scratch) {
+  const Tensor* d = &t[0];
+  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
+  OrdArgs o;
+  o.ws = P<uint8_t>(ws, U8, zk_tree_order_workspace(ncap), "order workspace",
+                    d);
+  o.ws_bytes = ws.numel();
+  o.passes = (int32_t)passes;
+  if (scratch.has_value() && scratch->defined()) {
+    const Tensor& sc = *scratch;
+    P<uint8_t>(sc, U8, 0, "scratch", d);
+    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
+                "zkmi: scratch must be a view of the tree's slab");
+    o.snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
+                            (const uint8_t*)t[6].data_ptr());
+    TORCH_CHECK(o.snap_base >= s.slab_cap && o.snap_base % 16 == 0,
+                "zkmi: scratch must start 16-aligned past the tree's slab");
+    o.snap_cap = sc.numel();
+  }
+  return o;
+}
+
 // [opcode, xid, err, node, zxid, path_off, path_len, path_arena, aux]
 ZkRespBatch resp_batch(const std::vector<Tensor>& v,
                        const c10::optional<Tensor>& slot, int64_t cap,
@@ -797,10 +879,7 @@ int64_t tree_order_stats_offset(int64_t n) {
 }
 
 // tree_serve with same-path requests applied in batch order over `passes`
-// launches.  `scratch` (optional) is the slab's tail past the tree's view of
-// it (t[6] = slab[:cap]); snapshot replies are written there and named by
-// their offset from the slab start, so the encoder must be given the whole
-// slab.
+// launches (ws, passes, scratch: ord_args).
 void tree_serve_ordered(const std::vector<Tensor>& t, const Tensor& rx,
                         const std::vector<Tensor>& q, const Tensor& n_dev,
                         int64_t ncap, const std::vector<Tensor>& r,
@@ -814,58 +893,17 @@ void tree_serve_ordered(const std::vector<Tensor>& t, const Tensor& rx,
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
   ZkReqOut qo = req_out(q, ncap, d);
   ZkServeOut ro = serve_out(r, ncap, d);
-  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
-  const int64_t need_ws = zk_tree_order_workspace(ncap);
-  uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
-  int64_t snap_base = 0, snap_cap = 0;
-  if (scratch.has_value() && scratch->defined()) {
-    const Tensor& sc = *scratch;
-    P<uint8_t>(sc, U8, 0, "scratch", d);
-    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
-                "zkmi: scratch must be a view of the tree's slab");
-    snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
-                          (const uint8_t*)t[6].data_ptr());
-    TORCH_CHECK(snap_base >= s.slab_cap && snap_base % 16 == 0,
-                "zkmi: scratch must start 16-aligned past the tree's slab");
-    snap_cap = sc.numel();
-  }
+  const OrdArgs o = ord_args(t, s, ncap, ws, passes, scratch);
   hip_ok(zk_tree_serve_ordered(
              &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
              P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, session,
-             now_ms, w, ws.numel(), (int32_t)passes, snap_base, snap_cap,
+             now_ms, o.ws, o.ws_bytes, o.passes, o.snap_base, o.snap_cap,
              (int32_t)wslot, Popt<int64_t>(fired, I64, 5 * ncap, "fired", d),
              cur_stream()),
          "tree_serve_ordered");
 }
 
 // -- session batches (csrc/kernels/tree_sess.hip) ---------------------------
-
-// The segment table of a session batch as the serves read it: f_seg [ncap],
-// and sessions / wslots / seg_state [S], bad [2].
-struct SegPtrs {
-  const int32_t* f_seg;
-  const int64_t* sessions;
-  const int32_t* wslots;
-  const int32_t* seg_state;
-  const int64_t* bad;
-  int64_t S;
-};
-
-SegPtrs seg_ptrs(const Tensor& f_seg, const Tensor& sessions,
-                 const Tensor& wslots, const Tensor& seg_state,
-                 const Tensor& bad, int64_t ncap, const Tensor* d) {
-  SegPtrs m;
-  m.S = sessions.numel();
-  TORCH_CHECK(m.S >= 1, "zkmi: a segment table has at least one segment");
-  m.f_seg = P<int32_t>(f_seg, I32, ncap, "f_seg", d);
-  m.sessions = P<int64_t>(sessions, I64, m.S, "sessions", d);
-  m.wslots = P<int32_t>(wslots, I32, m.S, "wslots", d);
-  TORCH_CHECK(wslots.numel() == m.S, "zkmi: wslots has ", wslots.numel(),
-              " entries, sessions ", m.S);
-  m.seg_state = P<int32_t>(seg_state, I32, m.S, "seg_state", d);
-  m.bad = P<int64_t>(bad, I64, 2, "bad", d);
-  return m;
-}
 
 // Frames -> segments, segments -> first frames and states, the table's
 // faults (zk_sess.h).  table: the session table's tensors for the liveness
@@ -903,147 +941,65 @@ void sess_assign(const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
          "sess_assign");
 }
 
-// tree_serve_frames for a session batch (no read-only form).
+// tree_serve_frames for a session batch (no read-only form); sg: segs().
 void tree_serve_frames_sessions(
     const std::vector<Tensor>& t, const Tensor& rx, const Tensor& foff,
     const Tensor& flen, const Tensor& n_dev, int64_t ncap,
     const std::vector<Tensor>& r, int64_t now_ms,
     const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
-    const Tensor& f_seg, const Tensor& sessions, const Tensor& wslots,
-    const Tensor& seg_state, const Tensor& bad) {
+    const std::vector<Tensor>& sg) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
   ZkServeOut ro = serve_out(r, ncap, d);
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
-  const SegPtrs m = seg_ptrs(f_seg, sessions, wslots, seg_state, bad, ncap, d);
+  const ZkSegs m = segs(sg, ncap, d);
   hip_ok(zk_tree_serve_frames_sessions(
              &s, P<uint8_t>(rx, U8, 1, "rx", d),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
              P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms,
-             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.f_seg,
-             m.sessions, m.wslots, m.seg_state, m.bad, m.S, cur_stream()),
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), &m,
+             cur_stream()),
          "tree_serve_frames_sessions");
 }
 
-// tree_serve_ordered for a session batch.
+// tree_serve_ordered for a session batch.  clip (ord_clip()): over the serve's
+// class of a session batch of any op mix, deferral in place of the rank
+// refusal (zk_order_clip.h); sg[0] is then the class's f_seg, the clip's
+// seg_c0.
 void tree_serve_ordered_sessions(
     const std::vector<Tensor>& t, const Tensor& rx,
     const std::vector<Tensor>& q, const Tensor& n_dev, int64_t ncap,
     const std::vector<Tensor>& r, int64_t now_ms, const Tensor& ws,
     int64_t passes, const c10::optional<Tensor>& scratch,
     const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
-    const Tensor& f_seg, const Tensor& sessions, const Tensor& wslots,
-    const Tensor& seg_state, const Tensor& bad) {
+    const std::vector<Tensor>& sg,
+    const c10::optional<std::vector<Tensor>>& clip) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
   s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
   ZkReqOut qo = req_out(q, ncap, d);
   ZkServeOut ro = serve_out(r, ncap, d);
-  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
-  const int64_t need_ws = zk_tree_order_workspace(ncap);
-  uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
-  int64_t snap_base = 0, snap_cap = 0;
-  if (scratch.has_value() && scratch->defined()) {
-    const Tensor& sc = *scratch;
-    P<uint8_t>(sc, U8, 0, "scratch", d);
-    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
-                "zkmi: scratch must be a view of the tree's slab");
-    snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
-                          (const uint8_t*)t[6].data_ptr());
-    TORCH_CHECK(snap_base >= s.slab_cap && snap_base % 16 == 0,
-                "zkmi: scratch must start 16-aligned past the tree's slab");
-    snap_cap = sc.numel();
-  }
-  const SegPtrs m = seg_ptrs(f_seg, sessions, wslots, seg_state, bad, ncap, d);
+  const OrdArgs o = ord_args(t, s, ncap, ws, passes, scratch);
+  const ZkSegs m = segs(sg, ncap, d);
+  ZkOrdClip c;
+  if (clip.has_value()) c = ord_clip(*clip, ncap, &m, d);
   hip_ok(zk_tree_serve_ordered_sessions(
              &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms, w,
-             ws.numel(), (int32_t)passes, snap_base, snap_cap,
-             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.f_seg,
-             m.sessions, m.wslots, m.seg_state, m.bad, m.S, cur_stream()),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms, o.ws,
+             o.ws_bytes, o.passes, o.snap_base, o.snap_cap,
+             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), &m,
+             clip.has_value() ? &c : nullptr, cur_stream()),
          "tree_serve_ordered_sessions");
 }
 
-// tree_serve_ordered_sessions over the serve's class of a session batch of any
-// op mix, with deferral (zk_order_clip.h): seg_c[0] is the class's f_seg; cls /
-// sub / count_all / f_seg_all are the whole batch's.
-void tree_serve_ordered_sessions_defer(
-    const std::vector<Tensor>& t, const Tensor& rx,
-    const std::vector<Tensor>& q, const Tensor& n_dev, int64_t ncap,
-    const std::vector<Tensor>& r, int64_t now_ms, const Tensor& ws,
-    int64_t passes, const c10::optional<Tensor>& scratch,
-    const c10::optional<Tensor>& fired, const c10::optional<Tensor>& seqno,
-    const Tensor& sessions, const Tensor& wslots, const Tensor& seg_state,
-    const Tensor& bad, const Tensor& cls, const Tensor& sub,
-    const Tensor& count_all, const Tensor& f_seg_all,
-    const std::vector<Tensor>& seg_c, const Tensor& clipf,
-    const Tensor& deferred) {
-  ZkTree s = tree(t);
-  const Tensor* d = &t[0];
-  s.seqno = Popt<int64_t>(seqno, I64, ncap, "seqno", d);
-  ZkReqOut qo = req_out(q, ncap, d);
-  ZkServeOut ro = serve_out(r, ncap, d);
-  TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
-  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1, "zkmi: ncap");
-  need(seg_c, 3, "seg_c");
-  const int64_t need_ws = zk_tree_order_workspace(ncap);
-  uint8_t* w = P<uint8_t>(ws, U8, need_ws, "order workspace", d);
-  int64_t snap_base = 0, snap_cap = 0;
-  if (scratch.has_value() && scratch->defined()) {
-    const Tensor& sc = *scratch;
-    P<uint8_t>(sc, U8, 0, "scratch", d);
-    TORCH_CHECK(sc.storage().is_alias_of(t[6].storage()),
-                "zkmi: scratch must be a view of the tree's slab");
-    snap_base = (int64_t)((const uint8_t*)sc.data_ptr() -
-                          (const uint8_t*)t[6].data_ptr());
-    TORCH_CHECK(snap_base >= s.slab_cap && snap_base % 16 == 0,
-                "zkmi: scratch must start 16-aligned past the tree's slab");
-    snap_cap = sc.numel();
-  }
-  const SegPtrs m =
-      seg_ptrs(seg_c[0], sessions, wslots, seg_state, bad, ncap, d);
-  hip_ok(zk_tree_serve_ordered_sessions_defer(
-             &s, P<uint8_t>(rx, U8, 1, "rx", d), &qo,
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &ro, now_ms, w,
-             ws.numel(), (int32_t)passes, snap_base, snap_cap,
-             Popt<int64_t>(fired, I64, 5 * ncap, "fired", d), m.sessions,
-             m.wslots, m.seg_state, m.bad, m.S,
-             P<int32_t>(cls, I32, ncap, "cls", d),
-             P<int32_t>(sub, I32, ncap, "sub", d),
-             P<int64_t>(count_all, I64, 1, "count_all", d),
-             P<int32_t>(f_seg_all, I32, ncap, "f_seg_all", d),
-             P<int32_t>(seg_c[0], I32, ncap, "seg_c[0]", d),
-             P<int32_t>(seg_c[1], I32, ncap, "seg_c[1]", d),
-             P<int32_t>(seg_c[2], I32, ncap, "seg_c[2]", d),
-             P<int64_t>(clipf, I64, m.S, "clipf", d),
-             P<int64_t>(deferred, I64, 1, "deferred", d), cur_stream()),
-         "tree_serve_ordered_sessions_defer");
-}
-
 // The deferral stage alone over a rank table of the caller's (uint8 [ncap]).
-void order_clip(const Tensor& rank, int64_t passes, const Tensor& cls,
-                const Tensor& sub, const Tensor& count_all, int64_t ncap,
-                const Tensor& f_seg_all, const std::vector<Tensor>& seg_c,
-                const Tensor& clipf, const Tensor& deferred) {
-  const Tensor* d = &rank;
+void order_clip(const Tensor& rank, int64_t passes, int64_t ncap,
+                const std::vector<Tensor>& clip) {
   TORCH_CHECK(passes >= 1 && passes <= 127, "zkmi: passes in 1..127");
-  TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1, "zkmi: order_clip ncap");
-  need(seg_c, 3, "seg_c");
-  const int64_t S = clipf.numel();
-  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
-              "zkmi: a segment table has at least one segment");
-  hip_ok(zk_order_clip(P<uint8_t>(rank, U8, ncap, "rank"), (int32_t)passes,
-                       P<int32_t>(cls, I32, ncap, "cls", d),
-                       P<int32_t>(sub, I32, ncap, "sub", d),
-                       P<int64_t>(count_all, I64, 1, "count_all", d), ncap,
-                       P<int32_t>(f_seg_all, I32, ncap, "f_seg_all", d),
-                       P<int32_t>(seg_c[0], I32, ncap, "seg_c[0]", d),
-                       P<int32_t>(seg_c[1], I32, ncap, "seg_c[1]", d),
-                       P<int32_t>(seg_c[2], I32, ncap, "seg_c[2]", d),
-                       P<int64_t>(clipf, I64, S, "clipf", d),
-                       P<int64_t>(deferred, I64, 1, "deferred", d), S,
-                       cur_stream()),
+  const ZkOrdClip c = ord_clip(clip, ncap, nullptr, &rank);
+  hip_ok(zk_order_clip(P<uint8_t>(rank, U8, ncap, "rank"), (int32_t)passes, &c,
+                       ncap, cur_stream()),
          "order_clip");
 }
 
@@ -1218,9 +1174,8 @@ int64_t watch_resume_sessions_workspace(int64_t ncap, int64_t ecap) {
 void watch_resume_sessions(const std::vector<Tensor>& t, const Tensor& rx,
                            const Tensor& foff, const Tensor& flen,
                            const Tensor& n_dev, int64_t ncap,
-                           const Tensor& f_seg, const Tensor& wslots,
-                           const Tensor& seg_state, const Tensor& bad,
-                           const Tensor& ws, const std::vector<Tensor>& ev,
+                           const std::vector<Tensor>& sg, const Tensor& ws,
+                           const std::vector<Tensor>& ev,
                            const Tensor& ev_total,
                            const std::vector<Tensor>& grouped,
                            const Tensor& slot_first, const Tensor& stats) {
@@ -1232,19 +1187,14 @@ void watch_resume_sessions(const std::vector<Tensor>& t, const Tensor& rx,
   need(grouped, 4, "grouped");
   TORCH_CHECK(ncap >= 1 && ncap < (1ll << 31) - 1,
               "zkmi: watch_resume_sessions ncap");
-  const int64_t S = wslots.numel();
-  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  const ZkSegs m = segs(sg, ncap, d);
   const int64_t ecap = ev[0].numel();
   TORCH_CHECK(ecap >= 1, "zkmi: watch_resume_sessions: no room for an event");
   hip_ok(zk_watch_resume_sessions(
              &s, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
-             P<int32_t>(wslots, I32, S, "wslots", d),
-             P<int32_t>(seg_state, I32, S, "seg_state", d),
-             P<int64_t>(bad, I64, 2, "bad", d), S,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m,
              P<int64_t>(ws, I64, zk_watch_resume_sessions_workspace(ncap, ecap),
                         "workspace", d),
              ecap, P<int32_t>(ev[0], I32, ecap, "ev_slot", d),
@@ -1478,22 +1428,20 @@ void tree_list(const std::vector<Tensor>& t, const Tensor& rx,
          "tree_list");
 }
 
-// tree_list for the list class of a session batch of any op mix: the class's
-// f_seg (sess_split_segments), the segments' wslots, sess_assign's seg_state
-// and bad in place of the watcher slot.
+// tree_list for the list class of a session batch of any op mix: the segment
+// table (segs(); f_seg: the class's, sess_split_segments) in place of the
+// watcher slot.
 void tree_list_sessions(const std::vector<Tensor>& t, const Tensor& rx,
                         const Tensor& foff, const Tensor& flen,
                         const Tensor& n_dev, int64_t ncap,
-                        const Tensor& f_seg, const Tensor& wslots,
-                        const Tensor& seg_state, const Tensor& bad,
-                        int64_t max_frame, const Tensor& want,
+                        const std::vector<Tensor>& sg, int64_t max_frame,
+                        const Tensor& want,
                         const Tensor& ws, const Tensor& out, int64_t out_cap,
                         const Tensor& rec_off, const Tensor& total,
                         const Tensor& err, bool terminate) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
-  const int64_t S = wslots.numel();
-  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  const ZkSegs m = segs(sg, ncap, d);
   TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1,
               "zkmi: tree_list_sessions ncap");
   TORCH_CHECK(max_frame >= 0, "zkmi: tree_list_sessions max_frame");
@@ -1506,11 +1454,7 @@ void tree_list_sessions(const std::vector<Tensor>& t, const Tensor& rx,
              &s, P<uint8_t>(rx, U8, 1, "rx", d),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
-             P<int32_t>(wslots, I32, S, "wslots", d),
-             P<int32_t>(seg_state, I32, S, "seg_state", d),
-             P<int64_t>(bad, I64, 2, "bad", d), S, max_frame,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m, max_frame,
              P<int32_t>(want, I32, s.store.cap, "want", d), w, ws.numel(),
              P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
              P<int64_t>(rec_off, I64, ncap, "rec_off", d),
@@ -1589,21 +1533,19 @@ void tree_acl_get(const std::vector<Tensor>& t,
 }
 
 // tree_acl_get for the GET_ACL class of a session batch of any op mix: the
-// class's f_seg (sess_split_segments), sess_assign's seg_state [S] and bad.
+// segment table (segs(); f_seg: the class's, sess_split_segments).
 void tree_acl_get_sessions(const std::vector<Tensor>& t,
                            const std::vector<Tensor>& acl, const Tensor& rx,
                            const Tensor& foff, const Tensor& flen,
                            const Tensor& n_dev, int64_t ncap,
-                           const Tensor& f_seg, const Tensor& seg_state,
-                           const Tensor& bad, const Tensor& ws,
+                           const std::vector<Tensor>& sg, const Tensor& ws,
                            const Tensor& out, int64_t out_cap,
                            const Tensor& rec_off, const Tensor& total,
                            const Tensor& err, bool terminate) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
   ZkAclTable a = acl_table(acl, d);
-  const int64_t S = seg_state.numel();
-  TORCH_CHECK(S >= 1, "zkmi: a segment table has at least one segment");
+  const ZkSegs m = segs(sg, ncap, d);
   TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
               " elements, needs ", s.store.cap);
   TORCH_CHECK(ncap >= 0 && ncap < (1ll << 28), "zkmi: tree_acl ncap");
@@ -1612,11 +1554,9 @@ void tree_acl_get_sessions(const std::vector<Tensor>& t,
              &s, &a, P<uint8_t>(rx, U8, 1, "rx", d),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
-             P<int32_t>(seg_state, I32, S, "seg_state", d),
-             P<int64_t>(bad, I64, 2, "bad", d), S, acl_ws(ws, ncap, d),
-             ws.numel(), P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m,
+             acl_ws(ws, ncap, d), ws.numel(),
+             P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
              P<int64_t>(rec_off, I64, ncap, "rec_off", d),
              P<int64_t>(total, I64, 1, "total", d),
              P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
@@ -2014,31 +1954,23 @@ int64_t close_workspace(int64_t cap_frames, int64_t S, int64_t node_cap) {
 // the frame table -> r_err (OK), the closing segments' list in ws, stats.
 void close_frames(const std::vector<Tensor>& t, const Tensor& rx,
                   const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
-                  int64_t ncap, const Tensor& f_seg, const Tensor& sessions,
-                  const Tensor& wslots, const Tensor& seg_state,
-                  const Tensor& bad, const Tensor& r_err, int64_t cap_frames,
-                  const Tensor& ws, const Tensor& stats) {
+                  int64_t ncap, const std::vector<Tensor>& sg,
+                  const Tensor& r_err, int64_t cap_frames, const Tensor& ws,
+                  const Tensor& stats) {
   ZkTree s = tree(t);
   const Tensor* d = &t[0];
-  const int64_t S = sessions.numel();
-  TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
-              "zkmi: a segment table has at least one segment");
+  const ZkSegs m = segs(sg, ncap, d);
   TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: close_frames ncap");
   TORCH_CHECK(cap_frames >= 0, "zkmi: close_frames cap_frames");
   hip_ok(zk_close_frames(
              &s, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
              P<int64_t>(foff, I64, ncap, "frame_off", d),
              P<int32_t>(flen, I32, ncap, "frame_len", d),
-             P<int64_t>(n_dev, I64, 1, "count", d), ncap,
-             P<int32_t>(f_seg, I32, ncap, "f_seg", d),
-             P<int64_t>(sessions, I64, S, "sessions", d),
-             P<int32_t>(wslots, I32, S, "wslots", d),
-             P<int32_t>(seg_state, I32, S, "seg_state", d),
-             P<int64_t>(bad, I64, 2, "bad", d), S,
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m,
              P<int32_t>(r_err, I32, ncap, "r_err", d), cap_frames,
              s.store.cap,
              P<int64_t>(ws, I64,
-                        zk_close_workspace(cap_frames, S, s.store.cap),
+                        zk_close_workspace(cap_frames, m.S, s.store.cap),
                         "workspace", d),
              P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
          "close_frames");
@@ -2304,26 +2236,14 @@ TORCH_LIBRARY(zkmi, m) {
   m.def("tree_serve_frames_sessions(Tensor(a!)[] tree, Tensor rx, "
         "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
         "Tensor(b!)[] out, int now_ms, Tensor(c!)? fired, Tensor? seqno, "
-        "Tensor f_seg, Tensor sessions, Tensor wslots, Tensor seg_state, "
-        "Tensor bad) -> ()", &tree_serve_frames_sessions);
+        "Tensor[] segs) -> ()", &tree_serve_frames_sessions);
   m.def("tree_serve_ordered_sessions(Tensor(a!)[] tree, Tensor rx, "
         "Tensor[] requests, Tensor count, int ncap, Tensor(b!)[] out, "
         "int now_ms, Tensor(c!) ws, int passes, Tensor? scratch, "
-        "Tensor(d!)? fired, Tensor? seqno, Tensor f_seg, Tensor sessions, "
-        "Tensor wslots, Tensor seg_state, Tensor bad) -> ()",
-        &tree_serve_ordered_sessions);
-  m.def("tree_serve_ordered_sessions_defer(Tensor(a!)[] tree, Tensor rx, "
-        "Tensor[] requests, Tensor count, int ncap, Tensor(b!)[] out, "
-        "int now_ms, Tensor(c!) ws, int passes, Tensor? scratch, "
-        "Tensor(d!)? fired, Tensor? seqno, Tensor sessions, Tensor wslots, "
-        "Tensor seg_state, Tensor bad, Tensor cls, Tensor sub, "
-        "Tensor count_all, Tensor(e!) f_seg_all, Tensor(f!)[] seg_c, "
-        "Tensor(g!) clipf, Tensor(h!) deferred) -> ()",
-        &tree_serve_ordered_sessions_defer);
-  m.def("order_clip(Tensor rank, int passes, Tensor cls, Tensor sub, "
-        "Tensor count_all, int ncap, Tensor(a!) f_seg_all, "
-        "Tensor(b!)[] seg_c, Tensor(c!) clipf, Tensor(d!) deferred) -> ()",
-        &order_clip);
+        "Tensor(d!)? fired, Tensor? seqno, Tensor[] segs, "
+        "Tensor(e!)[]? clip=None) -> ()", &tree_serve_ordered_sessions);
+  m.def("order_clip(Tensor rank, int passes, int ncap, Tensor(a!)[] clip) "
+        "-> ()", &order_clip);
   m.def("order_clip_ranges(Tensor clipf, Tensor rep_off, Tensor rec_off, "
         "Tensor frame_off, Tensor starts, Tensor count_all, int ncap, "
         "Tensor(a!) rep_end, Tensor(b!) used) -> ()", &order_clip_ranges);
@@ -2368,9 +2288,8 @@ TORCH_LIBRARY(zkmi, m) {
         "bool terminate=False) -> ()",
         &tree_list);
   m.def("tree_list_sessions(Tensor(a!)[] tree, Tensor rx, Tensor frame_off, "
-        "Tensor frame_len, Tensor count, int ncap, Tensor f_seg, "
-        "Tensor wslots, Tensor seg_state, Tensor bad, int max_frame, "
-        "Tensor(b!) want, Tensor(c!) ws, Tensor(d!) out, int out_cap, "
+        "Tensor frame_len, Tensor count, int ncap, Tensor[] segs, "
+        "int max_frame, Tensor(b!) want, Tensor(c!) ws, Tensor(d!) out, int out_cap, "
         "Tensor(e!) rec_off, Tensor(f!) total, Tensor(g!) err, "
         "bool terminate=False) -> ()",
         &tree_list_sessions);
@@ -2399,10 +2318,9 @@ TORCH_LIBRARY(zkmi, m) {
         &tree_acl_get);
   m.def("tree_acl_get_sessions(Tensor[] tree, Tensor[] acl, Tensor rx, "
         "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
-        "Tensor f_seg, Tensor seg_state, Tensor bad, Tensor(a!) ws, "
-        "Tensor(b!) out, int out_cap, Tensor(c!) rec_off, Tensor(d!) total, "
-        "Tensor(e!) err, bool terminate=False) -> ()",
-        &tree_acl_get_sessions);
+        "Tensor[] segs, Tensor(a!) ws, Tensor(b!) out, int out_cap, "
+        "Tensor(c!) rec_off, Tensor(d!) total, Tensor(e!) err, "
+        "bool terminate=False) -> ()", &tree_acl_get_sessions);
   m.def("watch_events(Tensor r_op, Tensor r_err, Tensor count, int ncap, "
         "Tensor fired, Tensor(a!) bsum, Tensor(b!) ev_slot, "
         "Tensor(c!) ev_type, Tensor(d!) ev_path_off, Tensor(e!) ev_path_len, "
@@ -2415,8 +2333,7 @@ TORCH_LIBRARY(zkmi, m) {
         &watch_resume_sessions_workspace);
   m.def("watch_resume_sessions(Tensor(a!)[] tree, Tensor rx, "
         "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
-        "Tensor f_seg, Tensor wslots, Tensor seg_state, Tensor bad, "
-        "Tensor(b!) ws, Tensor(c!)[] ev, Tensor(d!) ev_total, "
+        "Tensor[] segs, Tensor(b!) ws, Tensor(c!)[] ev, Tensor(d!) ev_total, "
         "Tensor(e!)[] grouped, Tensor(f!) slot_first, Tensor(g!) stats) "
         "-> ()", &watch_resume_sessions);
   m.def("watch_drop(Tensor(a!)[] tree, int wslot) -> ()", &watch_drop);
@@ -2473,8 +2390,7 @@ TORCH_LIBRARY(zkmi, m) {
   m.def("close_workspace(int cap_frames, int S, int node_cap) -> int",
         &close_workspace);
   m.def("close_frames(Tensor[] tree, Tensor rx, Tensor frame_off, "
-        "Tensor frame_len, Tensor count, int ncap, Tensor f_seg, "
-        "Tensor sessions, Tensor wslots, Tensor seg_state, Tensor bad, "
+        "Tensor frame_len, Tensor count, int ncap, Tensor[] segs, "
         "Tensor(a!) r_err, int cap_frames, Tensor(b!) ws, Tensor(c!) stats) "
         "-> ()", &close_frames);
   m.def("close_sessions(Tensor(a!)[] tree, Tensor? sids, Tensor? wslots, "

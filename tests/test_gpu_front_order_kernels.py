@@ -174,8 +174,9 @@ def dev_clip(dev, rank, cls, sub, f_seg, S, passes, nfr=None):
     d_c = [d(c, I32) for c in seg_c]
     clipf = torch.full((S,), -7, dtype=I64, device=dev)
     cnt = torch.full((1,), -7, dtype=I64, device=dev)
-    _lib.order_clip(d(rank, U8), passes, d(cls, I32), d(sub, I32),
-                    d([nfr], I64), ncap, d_seg, d_c, clipf, cnt)
+    _lib.order_clip(d(rank, U8), passes, ncap,
+                    [d(cls, I32), d(sub, I32), d([nfr], I64), d_seg, *d_c,
+                     clipf, cnt])
     return (clipf.cpu().tolist(), d_seg.cpu().tolist(),
             [c.cpu().tolist() for c in d_c], int(cnt.item()), seg_c)
 

@@ -826,8 +826,8 @@ def test_ops_check_their_tensors(gpu):
         a.update(kw)
         _lib.tree_serve_frames_sessions(
             tree.tensors, rx, z64(cap), z32(cap), z64(1), cap, out, 0, None,
-            None, a['f_seg'], a['sessions'], a['wslots'], a['seg_state'],
-            a['bad'])
+            None, [a['f_seg'], a['sessions'], a['wslots'], a['seg_state'],
+                   a['bad']])
 
     frames()
     for name, wrong in (('f_seg', z32(cap - 1)), ('wslots', z32(S + 1)),
@@ -841,10 +841,82 @@ def test_ops_check_their_tensors(gpu):
     with pytest.raises(RuntimeError):
         _lib.tree_serve_ordered_sessions(
             tree.tensors, rx, srv.rt.tensors(), z64(1), cap, out, 0, ows, 4,
-            tree.scratch, None, None, z32(cap), z64(S), z32(S + 1), z32(S),
-            z64(2))
+            tree.scratch, None, None, [z32(cap), z64(S), z32(S + 1), z32(S),
+                                       z64(2)])
     with pytest.raises(RuntimeError):
         _lib.tree_serve_ordered_sessions(
             tree.tensors, rx, srv.rt.tensors(), z64(1), cap, out, 0,
-            ows[:-1], 4, tree.scratch, None, None, z32(cap), z64(S), z32(S),
-            z32(S), z64(2))
+            ows[:-1], 4, tree.scratch, None, None, [z32(cap), z64(S), z32(S),
+                                                    z32(S), z64(2)])
+
+
+def test_segment_table_list_is_checked_once_for_all(gpu):
+    """Every op of a session batch takes the segment table as one list,
+    ``[f_seg, sessions, wslots, seg_state, bad]``, and refuses a malformed
+    one before it launches anything: its outputs stay zero."""
+    from zkmi.bench.synthetic import GpuServer, GpuTree
+    L = _lib.lib()
+    S, cap, ecap = 3, 256, 64
+    tree = GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,
+                   watch_cap=4096, scratch=1 << 20, acl_cap=512)
+    srv = GpuServer(tree, cap, 1 << 16)
+    srv._mix_buffers()
+    z64 = lambda n: torch.zeros(n, dtype=I64, device=gpu)     # noqa: E731
+    z32 = lambda n: torch.zeros(n, dtype=I32, device=gpu)     # noqa: E731
+    z8 = lambda n: torch.zeros(n, dtype=torch.uint8, device=gpu)  # noqa: E731
+    rec = lambda: [z32(ecap), z32(ecap), z64(ecap), z32(ecap)]    # noqa: E731
+    rx = z8(256)
+    foff, flen, count = z64(cap), z32(cap), z64(1)
+    good = [z32(cap), z64(S), z32(S), z32(S), z64(2)]
+    out = [z32(cap), z32(cap), z32(cap), z64(cap), z64(cap), z64(cap),
+           z32(cap), z64(cap), z64(cap), z64(1)]
+    ows = torch.ones(L.tree_order_workspace(cap), dtype=torch.uint8,
+                     device=gpu)
+    clip = [z32(cap), z32(cap), z64(1), z32(cap), good[0], z32(cap),
+            z32(cap), z64(S), z64(1)]
+    l_out, c_out = z8(4096), z8(4096)
+    l_res, c_res = [z64(cap), z64(1), z32(1)], [z64(cap), z64(1), z32(1)]
+    ev, grouped = rec(), rec()
+    rs = [z64(_lib.watch_resume_sessions_workspace(cap, ecap)), z64(2),
+          z64(65), z64(8)]
+    cl = [z32(cap), z64(_lib.close_workspace(cap, S, tree.cap)), z64(8)]
+
+    def ordered(sg, with_clip):
+        c = None
+        if with_clip:                     # (seg_c0 is the table's f_seg)
+            c = clip[:4] + [sg[0]] + clip[5:]
+        _lib.tree_serve_ordered_sessions(
+            tree.tensors, rx, srv.rt.tensors(), count, cap, out, 0, ows, 4,
+            tree.scratch, None, None, sg, c)
+
+    ops = [
+        lambda sg: _lib.tree_serve_frames_sessions(
+            tree.tensors, rx, foff, flen, count, cap, out, 0, None, None, sg),
+        lambda sg: ordered(sg, False),
+        lambda sg: ordered(sg, True),
+        lambda sg: _lib.tree_list_sessions(
+            tree.tensors, rx, foff, flen, count, cap, sg, 1 << 20,
+            srv.list_want, srv.list_ws, l_out, 4096, *l_res),
+        lambda sg: _lib.tree_acl_get_sessions(
+            tree.tensors, tree.acl, rx, foff, flen, count, cap, sg,
+            srv._acl_workspace(), c_out, 4096, *c_res),
+        lambda sg: _lib.watch_resume_sessions(
+            tree.tensors, rx, foff, flen, count, cap, sg, rs[0], ev, rs[1],
+            grouped, rs[2], rs[3]),
+        lambda sg: _lib.close_frames(
+            tree.tensors, rx, foff, flen, count, cap, sg, cl[0], cap, cl[1],
+            cl[2]),
+    ]
+    wrong = [good[:4], good + [z64(2)],
+             [good[0], good[1], z32(S + 1), good[3], good[4]],
+             [good[0], good[1], good[2], z64(S), good[4]]]
+    for op in ops:
+        for sg in wrong:
+            with pytest.raises(RuntimeError):
+                op(sg)
+    torch.cuda.synchronize()
+    outs = (out + clip + [l_out, c_out] + l_res + c_res + ev + grouped +
+            rs + cl + good)
+    assert not any(bool(t.any().item()) for t in outs)
+    assert bool((ows == 1).all().item())
+    assert bool((srv.list_want == _lib.LIST_IDLE).all().item())

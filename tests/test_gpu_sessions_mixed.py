@@ -761,12 +761,13 @@ def test_ops_check_their_tensors(gpu):
     rx = z8(64)
 
     def lists(**kw):
-        a = dict(f_seg=z32(cap), wslots=z32(S), seg_state=z32(S), bad=z64(2),
-                 want=srv.list_want, rec_off=z64(cap), out=z8(4096))
+        a = dict(f_seg=z32(cap), sessions=z64(S), wslots=z32(S),
+                 seg_state=z32(S), bad=z64(2), want=srv.list_want, rec_off=z64(cap), out=z8(4096))
         a.update(kw)
         _lib.tree_list_sessions(
-            tree.tensors, rx, z64(cap), z32(cap), z64(1), cap, a['f_seg'],
-            a['wslots'], a['seg_state'], a['bad'], 1 << 20, a['want'],
+            tree.tensors, rx, z64(cap), z32(cap), z64(1), cap,
+            [a['f_seg'], a['sessions'], a['wslots'], a['seg_state'],
+             a['bad']], 1 << 20, a['want'],
             srv.list_ws, a['out'], 4096, a['rec_off'], z64(1), z32(1))
 
     lists()
@@ -783,12 +784,14 @@ def test_ops_check_their_tensors(gpu):
     assert bool((srv.list_want == _lib.LIST_IDLE).all().item())
 
     def acls(**kw):
-        a = dict(f_seg=z32(cap), seg_state=z32(S), bad=z64(2),
-                 rec_off=z64(cap), out=z8(4096), ws=srv._acl_workspace())
+        a = dict(f_seg=z32(cap), sessions=z64(S), wslots=z32(S),
+                 seg_state=z32(S), bad=z64(2), rec_off=z64(cap),
+                 out=z8(4096), ws=srv._acl_workspace())
         a.update(kw)
         _lib.tree_acl_get_sessions(
             tree.tensors, tree.acl, rx, z64(cap), z32(cap), z64(1), cap,
-            a['f_seg'], a['seg_state'], a['bad'], a['ws'], a['out'], 4096,
+            [a['f_seg'], a['sessions'], a['wslots'], a['seg_state'],
+             a['bad']], a['ws'], a['out'], 4096,
             a['rec_off'], z64(1), z32(1))
 
     acls()

@@ -806,16 +806,16 @@ def test_op_checks_its_tensors(gpu):
     nws = _lib.watch_resume_sessions_workspace(cap, ecap)
     good = dict(rx=torch.zeros(256, dtype=torch.uint8, device=gpu),
                 frame_off=z64(cap), frame_len=z32(cap), count=z64(1),
-                f_seg=z32(cap), wslots=z32(S), seg_state=z32(S), bad=z64(2),
-                ws=z64(nws), ev=rec(), ev_total=z64(2), grouped=rec(),
+                f_seg=z32(cap), sessions=z64(S), wslots=z32(S),
+                seg_state=z32(S), bad=z64(2), ws=z64(nws), ev=rec(), ev_total=z64(2), grouped=rec(),
                 slot_first=z64(65), stats=z64(8))
 
     def call(ncap=cap, **kw):
         a = dict(good, **kw)
         _lib.watch_resume_sessions(
             tree.tensors, a['rx'], a['frame_off'], a['frame_len'], a['count'],
-            ncap, a['f_seg'], a['wslots'], a['seg_state'], a['bad'], a['ws'],
-            a['ev'], a['ev_total'], a['grouped'], a['slot_first'], a['stats'])
+            ncap, [a['f_seg'], a['sessions'], a['wslots'], a['seg_state'],
+                   a['bad']], a['ws'], a['ev'], a['ev_total'], a['grouped'], a['slot_first'], a['stats'])
 
     call()
     torch.cuda.synchronize()
@@ -849,7 +849,8 @@ def test_op_checks_its_tensors(gpu):
     with pytest.raises(RuntimeError):
         _lib.watch_resume_sessions(
             plain.tensors, good['rx'], good['frame_off'], good['frame_len'],
-            good['count'], cap, good['f_seg'], good['wslots'],
-            good['seg_state'], good['bad'], good['ws'], good['ev'],
+            good['count'], cap, [good['f_seg'], good['sessions'],
+                                 good['wslots'], good['seg_state'],
+                                 good['bad']], good['ws'], good['ev'],
             good['ev_total'], good['grouped'], good['slot_first'],
             good['stats'])

@@ -684,6 +684,22 @@ class _SegState(object):
             self.f_seg_c = [buf[c * cap:(c + 1) * cap] for c in range(3)]
         return self.f_seg_c
 
+    def table(self, segs, cls=None):
+        """The segment table as the session ops take it, ``[f_seg, sessions,
+        wslots, seg_state, bad]``, of :class:`SessionSegments` ``segs``: the
+        whole batch's, or with ``cls`` engine class ``cls``'s."""
+        f_seg = self.f_seg if cls is None else self.class_tables()[cls]
+        return [f_seg, segs.sessions, segs.wslots, self.state, self.bad]
+
+
+def _table_args(table):
+    """The keywords through which a session op takes a
+    :class:`GpuSessionTable` (or none)."""
+    if table is None:
+        return {'table': None, 'server_id': 0, 'span': 0}
+    return {'table': table._tensors, 'server_id': table.server_id,
+            'span': table.span}
+
 
 class GpuServer(object):
     """Server half of the pipeline: frame-scan + decode requests, apply them
@@ -1062,7 +1078,7 @@ class GpuServer(object):
         self.notif = (out, total, g['slot'], self.ev_total[0:1])
         self.notif_slots = (g['first'], g['off'])
 
-    def _resume_sessions(self, rx, ft, segs, rec_off, total, err):
+    def _resume_sessions(self, rx, ft, seg_table, rec_off, total, err):
         """The SET_WATCHES catch-up of the session batch just served
         (csrc/kernels/tree_resume.hip; the rules: zk_resume.h): every
         SET_WATCHES frame of ``ft`` for its own segment's watcher slot,
@@ -1104,8 +1120,8 @@ class GpuServer(object):
         b['resp'].path_arena = rx           # the encode arena: the requests
         _lib.watch_resume_sessions(
             self.tree.tensors, rx, ft.off, ft.length, ft.count,
-            self.cap_frames, sg.f_seg, segs.wslots, sg.state, sg.bad, b['ws'],
-            b['ev'], b['ev_total'], b['g'], b['first'], b['stats'])
+            self.cap_frames, seg_table, b['ws'], b['ev'], b['ev_total'],
+            b['g'], b['first'], b['stats'])
         out, _, rtotal, rerr = B.encode_responses(
             b['resp'], self.tree.store, b['buf'].numel(), out=b['buf'],
             total_err=b['total_err'], rec_off=b['rec_off'])
@@ -1251,7 +1267,6 @@ class GpuServer(object):
         ``close_notif`` slice), ``self.close_removed`` (int64 [S]: nodes
         removed for the k-th closing segment) and the counters of
         :meth:`close_stats`; nothing is read back."""
-        L = _lib.lib()
         if self.fused_rows or self.read_only:
             raise ValueError('serve_sessions: no session form of the '
                              'read-only or the fused-rows serve')
@@ -1264,66 +1279,96 @@ class GpuServer(object):
             self.seg = _SegState(self.cap_frames, segs.S, tree.device)
         sg = self.seg
         ft = self.scanner.scan(rx, n)
-        rt = B.decode_requests(rx, ft, out=self.rt) if ordered else None
-        _lib.sess_assign(
-            ft.off, ft.length, ft.count, self.cap_frames, segs.starts,
-            segs.sessions, sg.f_seg, sg.first, sg.state, sg.bad,
-            table=None if table is None else table._tensors,
-            server_id=0 if table is None else table.server_id,
-            span=0 if table is None else table.span)
+        _lib.sess_assign(ft.off, ft.length, ft.count, self.cap_frames,
+                         segs.starts, segs.sessions, sg.f_seg, sg.first,
+                         sg.state, sg.bad, **_table_args(table))
+        out, rec_off, total, err = self._serve_class(
+            rx, ft, sg.table(segs), segs, ordered, passes, None, close, None,
+            terminate)
+        self.last_rec_off = rec_off
+        self.result = (out, total, err, ft)
+        self._sessions_tail(rx, ft, segs, rec_off, total, err, table, resume,
+                            close, None)
+        return self.result
+
+    def _serve_class(self, rx, frames, seg_table, segs, ordered, passes,
+                     defer, close, rec_off, terminate):
+        """The serve of one class of a session batch's frames through to its
+        reply encode: ``frames`` with their segment table ``seg_table``
+        (:meth:`_SegState.table` of ``segs``) — the whole batch
+        (:meth:`serve_sessions`) or the serve's class
+        (:meth:`serve_sessions_mixed`).  ``defer``: the deferral's tables for
+        ``tree_serve_ordered_sessions`` or None; ``rec_off``: where the
+        encode leaves the frame starts (None: its own).  Returns what
+        ``encode_responses`` returns."""
+        L = _lib.lib()
+        tree = self.tree
+        cap = self.cap_frames
         r = self.resp
-        r.count = ft.count
+        r.count = frames.count
         out = [r.opcode, r.xid, r.err, r.node, r.zxid, r.path_off,
                r.path_len, r.slot, self.presized[0], self.presized[1]]
         now = int(time.time() * 1000)
-        seqno = self._seq_order(rx, ft) if self.seq_order else None
+        seqno = self._seq_order(rx, frames) if self.seq_order else None
         fired = self.fired if tree.watch is not None else None
         if ordered:
+            rt = B.decode_requests(rx, frames, out=self.rt)
             if self.ows is None:
-                self.ows = torch.empty(
-                    L.tree_order_workspace(self.cap_frames), dtype=U8,
-                    device=tree.device)
+                self.ows = torch.empty(L.tree_order_workspace(cap), dtype=U8,
+                                       device=tree.device)
             _lib.tree_serve_ordered_sessions(
-                tree.tensors, rx, rt.tensors(), ft.count, self.cap_frames,
-                out, now, self.ows, passes, tree.scratch, fired, seqno,
-                sg.f_seg, segs.sessions, segs.wslots, sg.state, sg.bad)
+                tree.tensors, rx, rt.tensors(), frames.count, cap, out, now,
+                self.ows, passes, tree.scratch, fired, seqno, seg_table,
+                defer)
         else:
             _lib.tree_serve_frames_sessions(
-                tree.tensors, rx, ft.off, ft.length, ft.count,
-                self.cap_frames, out, now, fired, seqno, sg.f_seg,
-                segs.sessions, segs.wslots, sg.state, sg.bad)
-            L.tree_finish_scan(tree.tensors, ft.count, 0, True,
-                               self.cap_frames, self.presized[1],
-                               self.total_err[0])
+                tree.tensors, rx, frames.off, frames.length, frames.count,
+                cap, out, now, fired, seqno, seg_table)
+            L.tree_finish_scan(tree.tensors, frames.count, 0, True, cap,
+                               self.presized[1], self.total_err[0])
         if tree.acl is not None:
-            _lib.tree_acl_record(tree.acl, rx, ft.off, ft.length, ft.count,
-                                 self.cap_frames, r.opcode, r.err, r.node,
+            _lib.tree_acl_record(tree.acl, rx, frames.off, frames.length,
+                                 frames.count, cap, r.opcode, r.err, r.node,
                                  self._acl_workspace())
         if close:
-            self._close_frames(rx, ft, sg.f_seg, segs)
-        out, rec_off, total, err = B.encode_responses(
+            self._close_frames(rx, frames, seg_table, segs.S)
+        enc = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
-            total_err=self.total_err, prescanned=not ordered)
+            total_err=self.total_err, prescanned=not ordered,
+            rec_off=rec_off)
         if tree.compact_free:
             tree.free_compact()
-        self.last_rec_off = rec_off
-        self.result = (out, total, err, ft)
-        if tree.watch is not None:
+        return enc
+
+    def _sessions_tail(self, rx, ft, segs, rec_off, total, err, table,
+                       resume, close, defer):
+        """What follows a session batch's replies (``rec_off`` / ``total`` /
+        ``err``: the whole batch's reply stream over frame table ``ft``): the
+        write-fired events, the reply and notification ranges, the
+        SET_WATCHES catch-up, the deferral's ranges (``defer``: the
+        :class:`OrderDefer` or None) and the close pass."""
+        sg = self.seg
+        cap = self.cap_frames
+        if self.tree.watch is not None:
             self._notify_grouped()
             g = self._grouped
-            _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
-                             total, err, sg.rep_off, g['first'],
-                             g['rec_off'], self.ev_total[0:1],
-                             g['total_err'][0], g['total_err'][1], g['off'])
+            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
+                             sg.rep_off, g['first'], g['rec_off'],
+                             self.ev_total[0:1], g['total_err'][0],
+                             g['total_err'][1], g['off'])
             if resume:
-                self._resume_sessions(rx, ft, segs, rec_off, total, err)
+                self._resume_sessions(rx, ft, sg.table(segs), rec_off, total,
+                                      err)
         else:
-            _lib.sess_ranges(sg.first, rec_off, ft.count, self.cap_frames,
-                             total, err, sg.rep_off)
+            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
+                             sg.rep_off)
+        if defer is not None:
+            _lib.order_clip_ranges(defer.clipf, sg.rep_off, rec_off, ft.off,
+                                   segs.starts, ft.count, cap, defer.rep_end,
+                                   defer.used)
         if close:
             self._close_batch(segs, table)
-        return self.result
 
     def session_stats(self):
         """Of the last :meth:`serve_sessions` or
@@ -1393,15 +1438,13 @@ class GpuServer(object):
             b['removed'] = torch.zeros(S, dtype=I64, device=dev)
         return b
 
-    def _close_frames(self, rx, frames, f_seg, segs):
+    def _close_frames(self, rx, frames, seg_table, S):
         """Pass 1 of a session batch served with ``close``: between the serve
         of ``frames`` and the encode of its replies."""
-        b = self._close_buffers(segs.S)
-        sg = self.seg
+        b = self._close_buffers(S)
         _lib.close_frames(self.tree.tensors, rx, frames.off, frames.length,
-                          frames.count, self.cap_frames, f_seg, segs.sessions,
-                          segs.wslots, sg.state, sg.bad, self.resp.err,
-                          self.cap_frames, b['ws'], b['stats'])
+                          frames.count, self.cap_frames, seg_table,
+                          self.resp.err, self.cap_frames, b['ws'], b['stats'])
 
     def _close_batch(self, segs, table):
         """Passes 2-7 of a session batch served with ``close``, over the list
@@ -1420,9 +1463,7 @@ class GpuServer(object):
         cap = self.cap_frames
         _lib.close_sessions(
             tree.tensors, sids, wslots, S, cap, b['ws'], removed, b['stats'],
-            table=None if table is None else table._tensors,
-            server_id=0 if table is None else table.server_id,
-            span=0 if table is None else table.span)
+            **_table_args(table))
         if tree.watch is None:
             return
         rec = b['ws'][:8 + 5 * cap]
@@ -1843,7 +1884,6 @@ class GpuServer(object):
 
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
-        L = _lib.lib()
         tree = self.tree
         if self.fused_rows or self.read_only:
             raise ValueError('serve_sessions_mixed: no session form of the '
@@ -1873,12 +1913,9 @@ class GpuServer(object):
         if max_frame is None:
             max_frame = consts.MAX_PACKET
         ft = self.scanner.scan(rx, n)
-        _lib.sess_assign(
-            ft.off, ft.length, ft.count, cap, segs.starts, segs.sessions,
-            sg.f_seg, sg.first, sg.state, sg.bad,
-            table=None if table is None else table._tensors,
-            server_id=0 if table is None else table.server_id,
-            span=0 if table is None else table.span)
+        _lib.sess_assign(ft.off, ft.length, ft.count, cap, segs.starts,
+                         segs.sessions, sg.f_seg, sg.first, sg.state, sg.bad,
+                         **_table_args(table))
         _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
                             tree.acl is not None, self.mix_cls, self.mix_sub,
                             self.mix_foff, self.mix_flen, self.mix_counts,
@@ -1887,66 +1924,27 @@ class GpuServer(object):
                                  ft.count, cap, seg_c)
         fa, fc, fl = self.mix_frames
         # the serve's class, as serve_sessions serves a batch
-        r = self.resp
-        r.count = fa.count
-        rout = [r.opcode, r.xid, r.err, r.node, r.zxid, r.path_off,
-                r.path_len, r.slot, self.presized[0], self.presized[1]]
-        now = int(time.time() * 1000)
-        seqno = self._seq_order(rx, fa) if self.seq_order else None
-        fired = self.fired if tree.watch is not None else None
-        if ordered:
-            rt = B.decode_requests(rx, fa, out=self.rt)
-            if self.ows is None:
-                self.ows = torch.empty(L.tree_order_workspace(cap), dtype=U8,
-                                       device=tree.device)
-            if defer is None:
-                _lib.tree_serve_ordered_sessions(
-                    tree.tensors, rx, rt.tensors(), fa.count, cap, rout, now,
-                    self.ows, passes, tree.scratch, fired, seqno, seg_c[0],
-                    segs.sessions, segs.wslots, sg.state, sg.bad)
-            else:
-                _lib.tree_serve_ordered_sessions_defer(
-                    tree.tensors, rx, rt.tensors(), fa.count, cap, rout, now,
-                    self.ows, passes, tree.scratch, fired, seqno,
-                    segs.sessions, segs.wslots, sg.state, sg.bad,
-                    self.mix_cls, self.mix_sub, ft.count, sg.f_seg, seg_c,
-                    defer.clipf, defer.deferred)
-        else:
-            _lib.tree_serve_frames_sessions(
-                tree.tensors, rx, fa.off, fa.length, fa.count, cap, rout, now,
-                fired, seqno, seg_c[0], segs.sessions, segs.wslots, sg.state,
-                sg.bad)
-            L.tree_finish_scan(tree.tensors, fa.count, 0, True, cap,
-                               self.presized[1], self.total_err[0])
-        if tree.acl is not None:
-            _lib.tree_acl_record(tree.acl, rx, fa.off, fa.length, fa.count,
-                                 cap, r.opcode, r.err, r.node,
-                                 self._acl_workspace())
-        if close:
-            self._close_frames(rx, fa, seg_c[0], segs)
-        a_out, _, a_total, a_err = B.encode_responses(
-            r, tree.store, self.out.numel(), out=self.out,
-            presized=self.presized, terminate=False,
-            total_err=self.total_err, prescanned=not ordered,
-            rec_off=self.mix_rec_off[0])
-        if tree.compact_free:
-            tree.free_compact()
+        clip = None if defer is None else [
+            self.mix_cls, self.mix_sub, ft.count, sg.f_seg, *seg_c,
+            defer.clipf, defer.deferred]
+        a_out, _, a_total, a_err = self._serve_class(
+            rx, fa, sg.table(segs, 0), segs, ordered, passes, clip, close,
+            self.mix_rec_off[0], False)
         # the two read engines, after the batch's writes
         c_out, l_out = self.mix_scratch
         c_total, c_err = self.acl_total_err
         if tree.acl is not None:
             _lib.tree_acl_get_sessions(
                 tree.tensors, tree.acl, rx, fc.off, fc.length, fc.count, cap,
-                seg_c[1], sg.state, sg.bad, self._acl_workspace(), c_out,
+                sg.table(segs, 1), self._acl_workspace(), c_out,
                 c_out.numel(), self.acl_rec_off, c_total, c_err, False)
         else:
             c_out = l_out
         l_total, l_err = self.list_total_err
         _lib.tree_list_sessions(
-            tree.tensors, rx, fl.off, fl.length, fl.count, cap, seg_c[2],
-            segs.wslots, sg.state, sg.bad, max_frame, self.list_want,
-            self.list_ws, l_out, l_out.numel(), self.list_rec_off, l_total,
-            l_err, False)
+            tree.tensors, rx, fl.off, fl.length, fl.count, cap,
+            sg.table(segs, 2), max_frame, self.list_want, self.list_ws, l_out,
+            l_out.numel(), self.list_rec_off, l_total, l_err, False)
         total, err = self.mix_total_err
         _lib.tree_mix_merge(
             self.mix_cls, self.mix_sub, ft.count, self.mix_counts, cap,
@@ -1958,24 +1956,8 @@ class GpuServer(object):
         rec_off = self.mix_rec_off[1]
         self.last_rec_off = rec_off
         self.result = (out, total, err, ft)
-        if tree.watch is not None:
-            self._notify_grouped()
-            g = self._grouped
-            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
-                             sg.rep_off, g['first'], g['rec_off'],
-                             self.ev_total[0:1], g['total_err'][0],
-                             g['total_err'][1], g['off'])
-            if resume:
-                self._resume_sessions(rx, ft, segs, rec_off, total, err)
-        else:
-            _lib.sess_ranges(sg.first, rec_off, ft.count, cap, total, err,
-                             sg.rep_off)
-        if defer is not None:
-            _lib.order_clip_ranges(defer.clipf, sg.rep_off, rec_off, ft.off,
-                                   segs.starts, ft.count, cap, defer.rep_end,
-                                   defer.used)
-        if close:
-            self._close_batch(segs, table)
+        self._sessions_tail(rx, ft, segs, rec_off, total, err, table, resume,
+                            close, defer)
         return self.result
 
     def acl_stats(self):

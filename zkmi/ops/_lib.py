@@ -284,60 +284,50 @@ def sess_assign(frame_off, frame_len, count, ncap, starts, sessions, f_seg,
 
 
 def tree_serve_frames_sessions(tree, rx, frame_off, frame_len, count, ncap,
-                               out, now_ms, fired, seqno, f_seg, sessions,
-                               wslots, seg_state, bad):
+                               out, now_ms, fired, seqno, segs):
     """``tree_serve_frames`` for a session batch: every frame is served for
-    its segment's session and watcher slot (:func:`sess_assign`'s outputs);
-    a batch with ``bad[0] != 0`` is refused SYSTEMERROR, a segment with state
-    :data:`SEG_EXPIRED` SESSION_EXPIRED.  ``tree_finish_scan`` follows."""
+    its segment's session and watcher slot.  ``segs``: the segment table,
+    ``[f_seg, sessions, wslots, seg_state, bad]`` — :func:`sess_assign`'s
+    outputs and the caller's sessions / wslots (int64 / int32 [S]); every op
+    of a session batch takes it in this form.  A batch with ``bad[0] != 0``
+    is refused SYSTEMERROR, a segment with state :data:`SEG_EXPIRED`
+    SESSION_EXPIRED.  ``tree_finish_scan`` follows."""
     lib().tree_serve_frames_sessions(tree, rx, frame_off, frame_len, count,
                                      int(ncap), out, int(now_ms), fired,
-                                     seqno, f_seg, sessions, wslots,
-                                     seg_state, bad)
+                                     seqno, list(segs))
 
 
 def tree_serve_ordered_sessions(tree, rx, requests, count, ncap, out, now_ms,
-                                ws, passes, scratch, fired, seqno, f_seg,
-                                sessions, wslots, seg_state, bad):
+                                ws, passes, scratch, fired, seqno, segs,
+                                clip=None):
     """``tree_serve_ordered`` for a session batch: requests on one path are
-    applied in stream order whichever segments they come from."""
-    lib().tree_serve_ordered_sessions(tree, rx, requests, count, int(ncap),
-                                      out, int(now_ms), ws, int(passes),
-                                      scratch, fired, seqno, f_seg, sessions,
-                                      wslots, seg_state, bad)
+    applied in stream order whichever segments they come from.
 
-
-def tree_serve_ordered_sessions_defer(tree, rx, requests, count, ncap, out,
-                                      now_ms, ws, passes, scratch, fired,
-                                      seqno, sessions, wslots, seg_state, bad,
-                                      cls, sub, count_all, f_seg_all, seg_c,
-                                      clipf, deferred):
-    """:func:`tree_serve_ordered_sessions` over the serve's class of a session
-    batch of any op mix (``requests`` / ``count``: the class's decoded
-    frames; ``seg_c[0]`` their segments), with deferral in place of the rank
-    refusal (csrc/kernels/tree_order.hip ord_clip_*; the rules:
+    ``clip`` (``[cls, sub, count_all, f_seg_all, seg_c0, seg_c1, seg_c2,
+    clipf, deferred]``): the serve's class of a session batch of any op mix
+    (``requests`` / ``count``: the class's decoded frames; ``segs[0]`` their
+    segments, the same tensor as ``seg_c0``), with deferral in place of the
+    rank refusal (csrc/kernels/tree_order.hip ord_clip_*; the rules:
     zk_order_clip.h).  Between the ranking and the first serve pass, three
     launches over the WHOLE batch's tables (``cls`` / ``sub``: the split's,
-    ``count_all``, ``f_seg_all``: :func:`sess_assign`'s, ``seg_c``: the three
+    ``count_all``, ``f_seg_all``: :func:`sess_assign`'s, ``seg_c*``: the three
     classes' segment tables): a frame of the serve's class whose rank is >=
     ``passes``, and every later frame of its segment, gets segment -1 in
-    ``f_seg_all`` and ``seg_c`` — every engine, the catch-up and the close
+    ``f_seg_all`` and ``seg_c*`` — every engine, the catch-up and the close
     pass refuse it without effect.  ``clipf`` (int64 [S]): the first deferred
     whole-batch frame of each segment (``ncap``: none); ``deferred`` (int64
     [1]): the frames deferred.  No host read."""
-    lib().tree_serve_ordered_sessions_defer(
-        tree, rx, requests, count, int(ncap), out, int(now_ms), ws,
-        int(passes), scratch, fired, seqno, sessions, wslots, seg_state, bad,
-        cls, sub, count_all, f_seg_all, list(seg_c), clipf, deferred)
+    lib().tree_serve_ordered_sessions(tree, rx, requests, count, int(ncap),
+                                      out, int(now_ms), ws, int(passes),
+                                      scratch, fired, seqno, list(segs),
+                                      None if clip is None else list(clip))
 
 
-def order_clip(rank, passes, cls, sub, count_all, ncap, f_seg_all, seg_c,
-               clipf, deferred):
-    """The deferral stage of :func:`tree_serve_ordered_sessions_defer` alone,
-    over a rank table of the caller's (uint8 [ncap], indexed by the serve
-    class's ``sub``; the low 7 bits are the rank)."""
-    lib().order_clip(rank, int(passes), cls, sub, count_all, int(ncap),
-                     f_seg_all, list(seg_c), clipf, deferred)
+def order_clip(rank, passes, ncap, clip):
+    """The deferral stage of :func:`tree_serve_ordered_sessions` alone
+    (``clip`` as there), over a rank table of the caller's (uint8 [ncap],
+    indexed by the serve class's ``sub``; the low 7 bits are the rank)."""
+    lib().order_clip(rank, int(passes), int(ncap), list(clip))
 
 
 def order_clip_ranges(clipf, rep_off, rec_off, frame_off, starts, count_all,
@@ -392,29 +382,29 @@ def sess_split_segments(f_seg, cls, sub, count, ncap, f_seg_c):
                               list(f_seg_c))
 
 
-def tree_list_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
-                       wslots, seg_state, bad, max_frame, want, ws, out,
-                       out_cap, rec_off, total, err, terminate=False):
-    """:func:`tree_list` for the list class of a session batch of any op mix:
+def tree_list_sessions(tree, rx, frame_off, frame_len, count, ncap, segs,
+                       max_frame, want, ws, out, out_cap, rec_off, total, err,
+                       terminate=False):
+    """:func:`tree_list` for the list class of a session batch of any op mix
+    (``segs``: the segment table with the class's ``f_seg``):
     frame i is served for segment ``f_seg[i]`` (its ``watch=1`` arms the
     child watch of ``wslots[f_seg[i]]``; outside 0..63: none); with
     ``bad[0] != 0`` every frame is refused SYSTEMERROR, a segment with state
     :data:`SEG_EXPIRED` SESSION_EXPIRED, header only and without effect."""
     lib().tree_list_sessions(tree, rx, frame_off, frame_len, count, int(ncap),
-                             f_seg, wslots, seg_state, bad, int(max_frame),
-                             want, ws, out, int(out_cap), rec_off, total, err,
+                             list(segs), int(max_frame), want, ws, out,
+                             int(out_cap), rec_off, total, err,
                              bool(terminate))
 
 
 def tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count, ncap,
-                          f_seg, seg_state, bad, ws, out, out_cap, rec_off,
-                          total, err, terminate=False):
+                          segs, ws, out, out_cap, rec_off, total, err,
+                          terminate=False):
     """:func:`tree_acl_get` for the GET_ACL class of a session batch of any
     op mix; refusals as :func:`tree_list_sessions`."""
     lib().tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count,
-                                int(ncap), f_seg, seg_state, bad, ws, out,
-                                int(out_cap), rec_off, total, err,
-                                bool(terminate))
+                                int(ncap), list(segs), ws, out, int(out_cap),
+                                rec_off, total, err, bool(terminate))
 
 
 # the SET_WATCHES catch-up of a session batch (csrc/kernels/tree_resume.hip;
@@ -433,9 +423,8 @@ def watch_resume_sessions_workspace(ncap, ecap):
     return lib().watch_resume_sessions_workspace(int(ncap), int(ecap))
 
 
-def watch_resume_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
-                          wslots, seg_state, bad, ws, ev, ev_total, grouped,
-                          slot_first, stats):
+def watch_resume_sessions(tree, rx, frame_off, frame_len, count, ncap, segs,
+                          ws, ev, ev_total, grouped, slot_first, stats):
     """The SET_WATCHES catch-up of a session batch, after its serve and on
     the current stream: every SET_WATCHES frame of the frame table is caught
     up for watcher slot ``wslots[f_seg[i]]`` against the tree as it is now.
@@ -448,9 +437,8 @@ def watch_resume_sessions(tree, rx, frame_off, frame_len, count, ncap, f_seg,
     outside the table, for a watcher slot outside 0..63, or for a frame that
     is not a well-formed SET_WATCHES.  No host read."""
     lib().watch_resume_sessions(tree, rx, frame_off, frame_len, count,
-                                int(ncap), f_seg, wslots, seg_state, bad, ws,
-                                list(ev), ev_total, list(grouped), slot_first,
-                                stats)
+                                int(ncap), list(segs), ws, list(ev), ev_total,
+                                list(grouped), slot_first, stats)
 
 
 # close / expire many sessions in one pass (csrc/kernels/tree_close.hip; the
@@ -469,9 +457,8 @@ def close_workspace(cap_frames, S, node_cap):
     return lib().close_workspace(int(cap_frames), int(S), int(node_cap))
 
 
-def close_frames(tree, rx, frame_off, frame_len, count, ncap, f_seg,
-                 sessions, wslots, seg_state, bad, r_err, cap_frames, ws,
-                 stats):
+def close_frames(tree, rx, frame_off, frame_len, count, ncap, segs, r_err,
+                 cap_frames, ws, stats):
     """Between a session batch's serve and its reply encode, on the current
     stream: every CLOSE_SESSION frame of a live segment of a sound table
     (``bad[0] == 0``, state :data:`SEG_SERVE`, a body of 8 bytes or more)
@@ -481,8 +468,7 @@ def close_frames(tree, rx, frame_off, frame_len, count, ncap, f_seg,
     :func:`close_sessions` without ``sids``.  ``stats`` (int64 [8]) is
     zeroed; ``stats[0]`` counts the closing frames.  No host read."""
     lib().close_frames(tree, rx, frame_off, frame_len, count, int(ncap),
-                       f_seg, sessions, wslots, seg_state, bad, r_err,
-                       int(cap_frames), ws, stats)
+                       list(segs), r_err, int(cap_frames), ws, stats)
 
 
 def close_sessions(tree, sids, wslots, S, cap_frames, ws, removed, stats,
