@@ -308,6 +308,9 @@ struct ServeSegs : ZkSegs {};
 // refused as a whole, so the numbers of its other SEQUENTIAL creates are in
 // use and a deferred one leaves its gap in the parent's cversion.
 static_assert(TR_T == FR_T, "a workgroup per block of FR_T frames");
+// the read-only TILES instance's frame image: 64 requests of the benchmark
+// (41 B bodies) are 2.9 KiB; a wave over 4 KiB reads global memory as ever
+constexpr int SRV_STAGE = 4096;
 template <bool PARSE, bool RO, bool TILES, bool MS = false, bool DEFER = false>
 ZK_DEV void tree_serve_body(
     const ZkTree& t, const uint8_t* __restrict__ rx, const ZkReqOut& q,
@@ -329,14 +332,32 @@ ZK_DEV void tree_serve_body(
   const bool in_batch = i < ncap && i < *n_dev;
   int64_t fo = 0;                    // the frame's row (TILES)
   int32_t fl = 0;
+  // where this lane reads its frame's bytes: rxs + (a stream offset inside
+  // the frame).  The read-only TILES instance (the GET pipeline's) stages the
+  // wave's frames in LDS first (zk_frame_rows.h FrSpan) and parses, hashes
+  // and compares the path there; offsets stay stream offsets.
+  const uint8_t* rxs = rx;
   if (TILES) {
     __shared__ FrLds rows;
     const int64_t nf = *n_dev;
-    if (fr_row(*T, blk, nf < ncap ? nf : ncap, rows, fo, fl)) {
+    const bool has = fr_row(*T, blk, nf < ncap ? nf : ncap, rows, fo, fl);
+    if (has) {
       rows_off[i] = fo;
       rows_len[i] = fl;
     }
     fr_housekeep(*T);
+    if constexpr (RO && TILES) {
+      __shared__ __attribute__((aligned(16)))
+          uint8_t img[TR_T / 64][fr_image_bytes<SRV_STAGE>()];
+      uint8_t* im = img[threadIdx.x >> 6];
+      const int lane = threadIdx.x & 63;
+      const int64_t n = stream_len(T->n_dev, T->n_cap);
+      FrSpan<SRV_STAGE> F;
+      fr_span_load(rx, n, has, fo, fl, lane, F);
+      int32_t rel;
+      if (fr_span_store(rx, n, F, im, lane, fo, rel))
+        rxs = (const uint8_t*)((uintptr_t)(const uint8_t*)im + rel - fo);
+    }
   }
   // ordered passes: this launch serves the requests of rank `pass`; the
   // last pass also answers any of a higher rank, refused (SYSTEMERROR: more
@@ -360,7 +381,7 @@ ZK_DEV void tree_serve_body(
   ReqFields rq{ST_BAD_DECODE, 0, OP_PING, 0, 0, 0, 0, -1, -1, -1, 0};
   if (live) {
     if (PARSE) {
-      rq = TILES ? parse_request(rx, fo, fl)
+      rq = TILES ? parse_request(rxs, fo, fl)
                  : parse_request(rx, foff[i], flen[i]);
     } else {
       rq.status = q.status[i];
@@ -388,7 +409,7 @@ ZK_DEV void tree_serve_body(
   L.path = nullptr;
   L.pl = L.dl = 0;
   if (ok_req) {
-    L.path = rx + rq.poff;
+    L.path = rxs + rq.poff;
     L.pl = rq.pl;
     L.dl = max(rq.dl, 0);
     L.flags = rq.arg;

@@ -14,6 +14,7 @@
 // rec_entry[t] through a staged copy of its bytes.
 #pragma once
 #include "zk_common.h"
+#include "zk_stage_span.h"
 
 namespace zk {
 
@@ -117,6 +118,117 @@ ZK_DEV void fr_stage_lean(const uint8_t* __restrict__ buf, int64_t n,
   __builtin_amdgcn_wave_barrier();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
+}
+
+// N dwords in memory order from byte p of an LDS image (N + 1 aligned
+// dwords + alignbyte; reads up to 4 bytes past p + 4 N).
+template <int N>
+ZK_DEV void lds_words(const uint8_t* sb, int32_t p, uint32_t (&w)[N]) {
+  const uint32_t* a = (const uint32_t*)(sb + (p & ~3));
+  uint32_t r[N + 1];
+#pragma unroll
+  for (int k = 0; k <= N; ++k) r[k] = a[k];
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    w[k] = __builtin_amdgcn_alignbyte(r[k + 1], r[k], p & 3);
+}
+
+ZK_DEV int64_t wave_uniform(int64_t x) {     // (x is the same in every lane)
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+  const uint32_t hi =
+      __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// ---- staging a wave's frames in LDS ----------------------------------------
+//
+// The lanes of a wave that hold consecutive rows (fo, fl), as fr_row hands
+// them out, own one contiguous span of the stream: from the first such
+// lane's fo to the last one's fo + fl.  fr_span_load + fr_span_store copy it
+// into the wave's own LDS image with 16-byte-per-lane coalesced loads
+// (zk_stage_span.h: the aligned chunks, the clipped head and tail; no byte
+// outside buf[0, n) is read, whatever buf's alignment), and hand each lane
+// the image offset of its body.  In two halves, so that a consumer can have
+// the loads of several spans in flight (a group of lanes each, one image
+// reused) before it waits for the first.
+//
+// IMG, the consumer's compile-time budget: the image's chunk bytes (a lane
+// holds IMG / 1024 chunks).  ONE decision per span, the same in every lane of
+// the wave: it is staged when some lane holds a row, every row lies inside
+// [s, e), the span lies inside the stream, and head + span fits IMG (a span
+// of IMG - 15 bytes always does).  Otherwise nothing is read or written and
+// the lanes read their frames from global memory as before.  Wave-private:
+// no workgroup barrier.
+template <int IMG>
+constexpr int fr_image_bytes() { return IMG + 16; }   // + lds_words' overhang
+
+template <int IMG>
+struct FrSpan {
+  static_assert(IMG % 1024 == 0, "whole chunks a lane");
+  static constexpr int PER = IMG / 1024;
+  StageSpan sp;
+  int64_t s;
+  bool ok;
+  uint4 v[PER];
+};
+
+// The decision, and (span inside the stream's aligned chunks: the common
+// case) every load of the lane issued.  mine: this lane holds a row of the
+// span.
+template <int IMG>
+ZK_DEV void fr_span_load(const uint8_t* __restrict__ buf, int64_t n, bool mine,
+                         int64_t fo, int32_t fl, int lane, FrSpan<IMG>& F) {
+  F.ok = false;
+  const uint64_t m = __ballot(mine);
+  if (m == 0) return;
+  const int first = (int)__builtin_ctzll(m);
+  const int last = 63 - (int)__builtin_clzll(m);
+  const int64_t s = wave_uniform(__shfl(fo, first, 64));
+  const int64_t e = wave_uniform(__shfl(fo + (fl > 0 ? fl : 0), last, 64));
+  if (!span_fits(s, e, n, IMG)) return;
+  const bool in = !mine || (fl >= 0 && fo >= s && fo + fl <= e);
+  if (__ballot(!in) != 0) return;
+  F.sp = span_make((uint64_t)(uintptr_t)buf, s, e, n);
+  F.s = s;
+  if (!span_image_fits(F.sp, IMG)) return;
+  F.ok = true;
+  if (F.sp.clipped) return;
+#pragma unroll
+  for (int j = 0; j < FrSpan<IMG>::PER; ++j) {
+    const int32_t c = lane + 64 * j;
+    F.v[j] = make_uint4(0, 0, 0, 0);
+    if (c < F.sp.nchunks)
+      __builtin_memcpy(&F.v[j], buf + span_chunk_off(F.sp, c), 16);
+  }
+}
+
+// The image written (img: 16-byte aligned, fr_image_bytes<IMG>()) and
+// visible to the wave; rel = the image offset of this lane's body.  False: the
+// span is not staged.
+template <int IMG>
+ZK_DEV bool fr_span_store(const uint8_t* __restrict__ buf, int64_t n,
+                          const FrSpan<IMG>& F, uint8_t* img, int lane,
+                          int64_t fo, int32_t& rel) {
+  if (!F.ok) return false;
+  if (!F.sp.clipped) {
+#pragma unroll
+    for (int j = 0; j < FrSpan<IMG>::PER; ++j) {
+      const int32_t c = lane + 64 * j;
+      if (c < F.sp.nchunks) *(uint4*)(img + 16 * c) = F.v[j];
+    }
+  } else {
+#pragma unroll 1
+    for (int32_t c = lane; c < F.sp.nchunks; c += 64) {
+      uint32_t w[4];
+      span_load_chunk(buf, n, F.sp, c, w);
+      *(uint4*)(img + 16 * c) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  rel = F.sp.head + (int32_t)(fo - F.s);
+  return true;
 }
 
 // Frame k (< cnt) of tile t from its recorded starts: start p and end q

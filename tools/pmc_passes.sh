@@ -1,7 +1,9 @@
 #!/bin/bash
 # PMC counter passes over one bench workload (default get), one rocprofv3 run
 # per pass (a pass holds at most 4 TCC counters: FETCH_SIZE uses 3 and
-# WRITE_SIZE 2, so they get separate passes).  Counters only with
+# WRITE_SIZE 2, so they get separate passes; the cache pass: L1 -> L2 read
+# requests, TA busy cycles, L2 hits / misses and L2 -> fabric read requests).
+# Counters only with
 # --kernel-trace (no sys/runtime traces, per the pool rules).  Summarise
 # with tools/pmc_summary.py.
 set -o pipefail
@@ -24,4 +26,6 @@ pass write WRITE_SIZE && \
 pass sq SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD \
   SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES && \
 pass lds SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES \
-  GRBM_GUI_ACTIVE
+  GRBM_GUI_ACTIVE && \
+pass cache TCP_TCC_READ_REQ_sum TA_BUSY_avr TCC_HIT_sum TCC_MISS_sum \
+  TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum GRBM_GUI_ACTIVE

@@ -1,7 +1,9 @@
 """Join the PMC passes of tools/pmc_passes.sh into one per-kernel table:
 median duration (kernel trace), HBM-side bytes fetched / written
 (FETCH_SIZE / WRITE_SIZE, KiB per dispatch), achieved GB/s, and the SQ
-instruction mix.  Usage: pmc_summary.py gpurun_out/pmc_get [out.md]."""
+instruction mix; a second table for the cache pass (L1 -> L2 read requests,
+TA busy, L2 hits / misses, L2 -> fabric read bytes).
+Usage: pmc_summary.py <the passes' output directory> [out.md]."""
 
 import collections
 import csv
@@ -36,6 +38,30 @@ def _load(d):
     return out
 
 
+def _cache_table(rows):
+    """The cache pass: L1 (TCP) -> L2 read requests (64 B each), TA busy
+    (average over the TAs, in GRBM_GUI_ACTIVE cycles of the same pass: the
+    share of the kernel's time), L2 hits / misses, and L2 -> fabric read
+    bytes (TCC_EA0_RDREQ: 32 B or 64 B each); the last column is L1 -> L2
+    read bytes over L2 -> fabric read bytes."""
+    lines = ['', '| kernel | median us | L1->L2 rd req | L1->L2 rd KiB | '
+             'TA busy % | L2 hit | L2 miss | L2->fabric rd KiB | L1/fabric |',
+             '|---|---|---|---|---|---|---|---|---|']
+    for dur, k, m in rows[:24]:
+        req = m.get('TCP_TCC_READ_REQ_sum', 0.0)
+        rd = m.get('TCC_EA0_RDREQ_sum', 0.0)
+        rd32 = m.get('TCC_EA0_RDREQ_32B_sum', 0.0)
+        ea = (32 * rd32 + 64 * (rd - rd32)) / 1024
+        gui = m.get('GRBM_GUI_ACTIVE', 0.0)
+        lines.append('| `%s` | %.1f | %.0f | %.0f | %.0f | %.0f | %.0f | '
+                     '%.0f | %.2f |' % (
+                         k, dur, req, req * 64 / 1024,
+                         100 * m.get('TA_BUSY_avr', 0.0) / gui if gui else 0,
+                         m.get('TCC_HIT_sum', 0), m.get('TCC_MISS_sum', 0),
+                         ea, req * 64 / 1024 / ea if ea else 0))
+    return lines
+
+
 def main(d, dst=None):
     data = _load(d)
     rows = []
@@ -61,6 +87,8 @@ def main(d, dst=None):
                          m.get('SQ_INSTS_VMEM_WR', 0),
                          m.get('SQ_LDS_BANK_CONFLICT', 0),
                          m.get('SQ_INSTS_MFMA', 0)))
+    if any('TCP_TCC_READ_REQ_sum' in m for _, _, m in rows):
+        lines += _cache_table(rows)
     txt = '\n'.join(lines) + '\n'
     if dst:
         open(dst, 'w').write(txt)
