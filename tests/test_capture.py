@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _tree(gpu, scratch=0, **kw):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     return GpuTree(20000, 37, fanout=100, device=gpu, spare=1.0,
                    scratch=scratch, **kw)
 
@@ -104,7 +104,8 @@ def test_watch_replays_a_cycle(gpu):
     """Arm, write-fired notifications and their decode + check, replayed:
     every replay's notifications all arrive and check out (the watches
     re-arm every step, so a cycle's node sets can repeat)."""
-    from zkmi.bench.synthetic import GpuTree, WatchPipeline
+    from zkmi.bench.synthetic import WatchPipeline
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(20000, 37, fanout=100, device=gpu, seed=0,
                    watch_cap=8192)
     pipe = WatchPipeline(tree, 3000)

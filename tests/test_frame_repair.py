@@ -256,7 +256,8 @@ def test_get_replies_exact_below_the_largest_frame(gpu, monkeypatch):
     from zkmi.ops import batch as B
     monkeypatch.setattr(B, 'FS_WINDOW_AUTO_MAX', 512)
     from zkmi.bench import synthetic as S
-    tree = S.GpuTree(200_000, 100, device=gpu, seed=0, data_dist=(0, 1024))
+    from zkmi.server.tree import GpuTree
+    tree = GpuTree(200_000, 100, device=gpu, seed=0, data_dist=(0, 1024))
     pipe = S.GetPipeline(tree, 1 << 16, seed=1)
     from zkmi.ops import batch as B
     assert pipe.rwindow == 512 | B.FS_WIN_LONG
@@ -328,7 +329,8 @@ def test_big_repair_beside_another_connection(gpu):
     queued behind the other stream's kernels, which drain in microseconds;
     the scan stays exact and far below the barrier's 0.5 s abandon (no
     fallback to the serial repair)."""
-    from zkmi.bench.synthetic import GpuTree, GetPipeline
+    from zkmi.bench.synthetic import GetPipeline
+    from zkmi.server.tree import GpuTree
     rng = np.random.default_rng(29)
     lens = rng.integers(88, 1113, 60000)
     buf, starts = _stream(rng, lens)

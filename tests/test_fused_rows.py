@@ -97,20 +97,20 @@ _trees = {}
 def _tree(gpu, key, **kw):
     """Two identical small trees per key (the plain and the fused server's:
     a serve advances its tree's zxid)."""
-    from zkmi.bench import synthetic as S
+    from zkmi.server.tree import GpuTree
     if key not in _trees:
         # (one creation time: the nodes' ctime / mtime are in every Stat)
-        _trees[key] = tuple(S.GpuTree(device=gpu, seed=0,
-                                      ctime_ms=1_700_000_000_000, **kw)
+        _trees[key] = tuple(GpuTree(device=gpu, seed=0,
+                                    ctime_ms=1_700_000_000_000, **kw)
                             for _ in range(2))
     return _trees[key]
 
 
 def _servers(gpu, cap):
-    from zkmi.bench import synthetic as S
+    from zkmi.server.engine import GpuServer
     ta, tb = _tree(gpu, 'srv', n_nodes=2000, data_bytes=37)
-    mk = lambda t, f: S.GpuServer(t, cap, cap * 160 + 64,      # noqa: E731
-                                  seq_order=False, fused_rows=f)
+    mk = lambda t, f: GpuServer(t, cap, cap * 160 + 64,        # noqa: E731
+                                seq_order=False, fused_rows=f)
     sa, sb = mk(ta, False), mk(tb, True)
     sa.read_only = sb.read_only = True
     return sa, sb
@@ -206,7 +206,8 @@ def test_get_on_an_acl_tree_stays_plain(gpu):
     """A tree with an ACL table: the serve may not be fused, and the reply
     side stays on the three-launch scan with it."""
     from zkmi.bench import synthetic as S
-    tree = S.GpuTree(2000, 37, device=gpu, seed=0, acl_cap=4)
+    from zkmi.server.tree import GpuTree
+    tree = GpuTree(2000, 37, device=gpu, seed=0, acl_cap=4)
     pipe = S.GetPipeline(tree, 3000, seed=3)
     assert not pipe.server.fused_rows
     for _ in range(2):
@@ -356,11 +357,11 @@ def test_consumer_leaves_the_workspace_clean(gpu, xt):
 
 
 def test_fused_serve_only_as_first_reader(gpu):
-    from zkmi.bench import synthetic as S
+    from zkmi.server.engine import GpuServer
     ta, _ = _tree(gpu, 'srv', n_nodes=2000, data_bytes=37)
     with pytest.raises(ValueError):
-        S.GpuServer(ta, 256, 1 << 16, seq_order=True, fused_rows=True)
-    srv = S.GpuServer(ta, 256, 1 << 16, seq_order=False, fused_rows=True)
+        GpuServer(ta, 256, 1 << 16, seq_order=True, fused_rows=True)
+    srv = GpuServer(ta, 256, 1 << 16, seq_order=False, fused_rows=True)
     rx = torch.zeros(8192, dtype=torch.uint8, device=gpu)
     with pytest.raises(ValueError):
         srv.serve(rx, 8192, ordered=True)

@@ -140,7 +140,8 @@ def _acl_vectors(k):
 
 
 def _setup(gpu, n=300, fanout=100, frames=1024, **kw):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     kw.setdefault('acl_cap', 512)
     kw.setdefault('spare', 4.0)
     tree = GpuTree(n, 16, fanout=fanout, device=gpu, **kw)
@@ -423,7 +424,7 @@ def test_replicas(gpu, monkeypatch):
     differ): their GET_ACL reply streams for all created paths are
     byte-equal."""
     import time
-    from zkmi.bench import synthetic as S
+    from zkmi.server import engine as S
     monkeypatch.setattr(S, 'time', types.SimpleNamespace(
         time=lambda: 1.7e9, perf_counter=time.perf_counter,
         sleep=time.sleep))
@@ -529,7 +530,8 @@ def test_op_argument_checks(gpu):
 def test_no_acl_table(gpu):
     """A tree without an ACL table: serve_acl raises, and serve() answers a
     create batch as a tree with one does."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     a, b = _acl_vectors(2)
     pk = [_create(10 + i, '/bench/d000000/p%02d' % i, a if i % 2 else b)
           for i in range(40)]
@@ -558,7 +560,9 @@ def test_acl_pipeline_capture_replay(gpu):
     replayed three times; the device check stays clean and the first
     replay's replies decode to the same (xid, acl) list as the eager
     step's."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer, AclPipeline, MIX_ACLS
+    from zkmi.bench.synthetic import AclPipeline, MIX_ACLS
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(20_000, 16, fanout=100, device=gpu, acl_cap=16)
     srv = GpuServer(tree, 256, 1 << 18, window=512)
     second = MIX_ACLS[1]

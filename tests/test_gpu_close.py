@@ -155,7 +155,8 @@ class CloseWatchModel(_Close, WatchModel):
 def _tree(gpu, cls=CloseModel, cap_frames=1024, **kw):
     """The churn tests' smallest tree: 12 static nodes, 1024 spare, 4096
     index entries (the windowed names are chosen for this table size)."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0, **kw)
     assert (tree.cap, tree.hcap) == (1036, HCAP)
     srv = GpuServer(tree, cap_frames, 1 << 20)
@@ -382,7 +383,9 @@ def close_req():
 
 
 def _watch_tree(gpu, table=False):
-    from zkmi.bench.synthetic import GpuTree, GpuServer, GpuSessionTable
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.sessions import GpuSessionTable
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0, watch_cap=1024,
                    scratch=1 << 16)
     srv = GpuServer(tree, 256, 1 << 18)
@@ -405,7 +408,7 @@ def _sids(tab):
 def _batch(dev, segs, starts=None):
     """segs: [(session, watcher slot, [request dict or raw frame bytes])]
     -> (rx, its length, the segment table); xids count from 1 a segment."""
-    from zkmi.bench.synthetic import SessionSegments
+    from zkmi.server.engine import SessionSegments
     parts = []
     for _, _, pk in segs:
         b = b''
@@ -459,6 +462,60 @@ def _kids(tree, path):
 
 def _zxid(tree):
     return int(tree.counters[_lib.TC_ZXID].item())
+
+
+def test_three_streams_keep_their_buffers(gpu):
+    """One batch that fills all three notification streams — a write to a
+    node another segment watches (write-fired), a SET_WATCHES that lists a
+    node changed since relZxid 0 (catch-up), a CLOSE_SESSION whose segment
+    owns an ephemeral under a directory another segment's list watches
+    (close-fired) — served twice with the same ``rx`` shape: the second call
+    allocates nothing, every published tensor is where the first left it."""
+    tree, srv, _ = _watch_tree(gpu)
+    s0, s1, s2 = _sids(None)[:3]
+    na, nb, nc = (D0 + '/n%09d' % k for k in (1, 2, 3))
+    mine = D0 + '/mine'
+    rx, n, sg = _batch(gpu, [(s0, 5, [wget(na)])])
+    _serve(srv, 'mixed', rx, n, sg)
+    shapes, ptrs = [], []
+    # (the data watch a call arms is on the node the next call writes: a
+    # watch armed in the write's own batch may be fired by it.  The list's
+    # child watch is armed after the batch's writes and before its close
+    # pass, whose removal of ``mine`` fires it.)
+    for arm, write in ((nb, na), (na, nb)):
+        rx, n, sg = _batch(gpu, [
+            (s0, 5, [wget(arm), ls(D0)]),
+            (s1, 9, [set_data(write, b'w')]),
+            (s2, 7, [create(mine, b'm', ['EPHEMERAL']),
+                     {'opcode': 'SET_WATCHES', 'relZxid': 0,
+                      'events': {'dataChanged': [nc],
+                                 'createdOrDestroyed': [],
+                                 'childrenChanged': []}},
+                     close_req()])])
+        reps = _serve(srv, 'mixed', rx, n, sg, resume=True, close=True)
+        assert all(e == OK for rs in reps for _, _, e in rs), reps
+        shapes.append((n, sg.S))
+        streams = ((srv.notif, srv.notif_slots),
+                   (srv.resume_notif, srv.resume_slots),
+                   (srv.close_notif, srv.close_slots))
+        assert all(int(nf[1].item()) > 0 for nf, _ in streams)
+        ptrs.append([t.data_ptr() for nf, sl in streams
+                     for t in (nf[0],) + tuple(sl)])
+        fired, caught, closed = (slot_events(nf, sl) for nf, sl in streams)
+        assert ('DATA_CHANGED', write) in fired[5]
+        assert caught == {7: [('DATA_CHANGED', nc)]}
+        assert closed == {5: [('CHILDREN_CHANGED', D0)]}
+        assert _kids(tree, D0).count('mine') == 0
+    assert shapes[0] == shapes[1] and ptrs[0] == ptrs[1]
+    assert set(srv.watch_stats()) == {
+        'lost_arms', 'events_fired', 'events_written', 'encode_err',
+        'expiry_dropped', 'resume_dropped', 'resume_err'}
+    assert set(srv.resume_stats()) == {
+        'events', 'events_written', 'rearmed', 'listed', 'dropped',
+        'no_slot', 'encode_err'}
+    assert set(srv.close_stats()) == {
+        'frames', 'sessions', 'removed', 'events_fired', 'events_written',
+        'records_dropped', 'encode_err'}
 
 
 HOWS = ('sessions', 'ordered', 'mixed')
@@ -671,7 +728,7 @@ def test_close_off_is_unchanged(gpu, how):
 def test_close_op_checks(gpu):
     """A wrong dtype, device, length or a non-contiguous tensor to
     torch.ops.zkmi.close_sessions raises before anything is launched."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0)
     cap, S = 64, 4
     ws = torch.empty(_lib.close_workspace(cap, S, tree.cap), dtype=I64,

@@ -211,7 +211,7 @@ def test_fused_check_counts_only_clean_gets(replies, gpu):
     GET_DATA successes with the request's xid, the node's czxid and data
     length, as the host counts them from the oracle's packets; no mutated
     row is among them.  The reply table is the unchecked decode's."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.ops import batch as B
     R = replies
     tree = GpuTree(100, NODES[2], fanout=10, device=gpu)
@@ -341,14 +341,15 @@ def _leaf(i):
 def _fixed_clock(monkeypatch):
     """Both replicas stamp the same mtime / ctime."""
     import time
-    from zkmi.bench import synthetic as S
+    from zkmi.server import engine as S
     monkeypatch.setattr(S, 'time', types.SimpleNamespace(
         time=lambda: 1.7e9, perf_counter=time.perf_counter,
         sleep=time.sleep))
 
 
 def _replica(gpu, **kw):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(4000, 16, fanout=100, device=gpu, spare=1.0,
                    ctime_ms=1600000000000, **kw)
     return tree, GpuServer(tree, 1024, 1 << 20, window=256)

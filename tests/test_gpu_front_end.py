@@ -24,7 +24,7 @@ STAT_FIELDS = ('version', 'cversion', 'aversion', 'dataLength', 'numChildren')
 
 
 def _make(gpu, table=None, **kw):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.server.gpu import GpuZKServer
     tree = GpuTree(n_nodes=2000, fanout=100, watch_cap=4096, acl_cap=64,
                    device=gpu)
@@ -325,7 +325,7 @@ class Raw(object):
 # ---- 5. session expiry -----------------------------------------------------------
 
 def test_expiry_and_close_session(gpu):
-    from zkmi.bench.synthetic import GpuSessionTable
+    from zkmi.server.sessions import GpuSessionTable
 
     def table(tree):
         t = GpuSessionTable(tree)

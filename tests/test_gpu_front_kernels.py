@@ -310,7 +310,7 @@ def test_gather_skips_a_piece_outside_its_stream(gpu):
 # ---- the assembly --------------------------------------------------------------
 
 def _batch(dev, segs):
-    from zkmi.bench.synthetic import SessionSegments
+    from zkmi.server.engine import SessionSegments
     parts = []
     for _, _, pk in segs:
         for k, p in enumerate(pk):
@@ -336,7 +336,8 @@ def test_tx_assembly_of_a_real_batch(gpu):
     one that closes: every connection's TX span is its replies, then its
     watcher slot's catch-up, write-fired and close-fired slices, taken on the
     host from out / rep_off and the three slot_off tables."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0, watch_cap=1024,
                    scratch=1 << 16)
     srv = GpuServer(tree, 256, 1 << 18)

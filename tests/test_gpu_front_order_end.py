@@ -21,7 +21,7 @@ STAT_FIELDS = ('version', 'cversion', 'aversion', 'dataLength', 'numChildren')
 
 
 def _make(gpu, **kw):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.server.gpu import GpuZKServer
     tree = GpuTree(n_nodes=2000, fanout=100, watch_cap=4096, acl_cap=64,
                    scratch=kw.pop('scratch', 1 << 20), device=gpu)
@@ -107,7 +107,7 @@ def _script(c):
 
 
 def test_ordered_mode_needs_a_scratch_tail(gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.server.gpu import GpuZKServer
     tree = GpuTree(n_nodes=200, fanout=100, watch_cap=1024, device=gpu)
     with pytest.raises(ValueError):

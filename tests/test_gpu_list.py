@@ -99,7 +99,8 @@ def test_static_tree_lists(gpu, fanout):
     0), a missing path and / (NO_NODE: the tree has no root node), a
     GET_DATA frame (UNIMPLEMENTED) and a truncated frame (BAD_ARGUMENTS) in
     the same batch.  Replies come in request order with the request xids."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     n = max(5 * fanout + 3, 40)
     tree = GpuTree(n, 16, fanout=fanout, device=gpu)
     srv = GpuServer(tree, 256, 1 << 20, window=256)
@@ -143,7 +144,8 @@ def test_static_tree_lists(gpu, fanout):
 def test_unaligned_names(gpu):
     """Names of 10..47 bytes (name_pad): every child of 20 directories byte
     for byte, and the reply stream frames exactly (checked in _decode)."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(20 * 37, 16, fanout=37, device=gpu, name_pad=(0, 37))
     srv = GpuServer(tree, 64, 1 << 20, window=256)
     model = _path_model(tree)
@@ -161,7 +163,8 @@ def test_duplicate_parents(gpu):
     """One parent asked five times in a batch (opcodes 8 and 12 in turn)
     between other parents: every copy is complete, the per-node claim words
     are idle again afterwards, and the next batch is right."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(2000, 16, fanout=100, device=gpu)
     srv = GpuServer(tree, 64, 1 << 20, window=256)
     model = _path_model(tree)
@@ -193,7 +196,8 @@ def test_lists_follow_writes(gpu):
     serve(): after each stage every touched parent lists its model, agrees
     with its numChildren and with GpuTree.children_host, and no freed node
     shows."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(200, 16, fanout=20, device=gpu, spare=2.0)
     srv = GpuServer(tree, 256, 1 << 20, window=512)
     model = _path_model(tree)
@@ -274,7 +278,8 @@ def test_list_arms_child_watch(gpu):
     """A list with watch=1 arms the one-shot child watch of the caller's
     watcher slot: the next create under the directory notifies slot 3 once,
     a second create nothing; a listed missing path arms nothing."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(300, 16, fanout=100, device=gpu, watch_cap=256)
     srv = GpuServer(tree, 64, 1 << 18, window=256)
     d0, d1 = '/bench/d000000', '/bench/d000001'
@@ -297,7 +302,8 @@ def test_list_arms_child_watch(gpu):
 
 
 def _limit_setup(gpu):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(250, 16, fanout=100, device=gpu)
     srv = GpuServer(tree, 64, 1 << 18, window=256)
     return tree, srv
@@ -381,7 +387,8 @@ def test_empty_batch_and_terminator(gpu):
 
 
 def test_sharded_tree_refused(gpu):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(200, 16, fanout=100, device=gpu, shard=(0, 2))
     srv = GpuServer(tree, 64, 1 << 16, window=256)
     s = _frames([_ls(1, '/bench/d000000')])
@@ -437,7 +444,8 @@ def test_list_pipeline_capture_replay(gpu):
     """ListPipeline on a 20k-node tree: an eager step, then the captured
     step replayed three times; the device check stays clean and the first
     replay's replies decode to the same children as the eager step's."""
-    from zkmi.bench.synthetic import GpuTree, ListPipeline
+    from zkmi.bench.synthetic import ListPipeline
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(20_000, 16, fanout=100, device=gpu)
     pipe = ListPipeline(tree, 512)            # 200 directories, duplicates
 

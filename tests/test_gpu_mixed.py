@@ -149,7 +149,8 @@ def _compare(x, y, cls):
 
 
 def _pair(gpu, fanout, frames=1024, acl=True, watch=True):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     out = []
     for _ in range(2):
         tree = GpuTree(LEAVES[fanout], 16, fanout=fanout, device=gpu,
@@ -458,7 +459,8 @@ def test_empty_batch_with_terminator(gpu):
 
 
 def test_refusals(gpu):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     rx = torch.zeros(64, dtype=torch.uint8, device=gpu)
     tree = GpuTree(100, 16, fanout=10, device=gpu)
     srv = GpuServer(tree, 64, 1 << 16, seq_order=False, fused_rows=True)

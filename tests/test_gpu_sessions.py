@@ -51,7 +51,7 @@ def dirp(d):
 
 
 def _segments(dev, starts, sessions, wslots):
-    from zkmi.bench.synthetic import SessionSegments
+    from zkmi.server.engine import SessionSegments
     return SessionSegments(
         torch.tensor(list(starts), dtype=I64, device=dev),
         torch.tensor(list(sessions), dtype=I64, device=dev),
@@ -59,7 +59,7 @@ def _segments(dev, starts, sessions, wslots):
 
 
 def _tree(gpu, **kw):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     return GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,
                    watch_cap=4096, scratch=1 << 20, **kw)
 
@@ -230,7 +230,7 @@ class SessModel(WatchModel):
 
 
 def _model(gpu, frames=1024):
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _tree(gpu)
     srv = GpuServer(tree, frames, 1 << 21)
     return SessModel(tree, srv, gpu)
@@ -419,7 +419,7 @@ def test_model_ordered(gpu):
 # ---- 3. differential: one session batch against a serve a segment -----------
 
 def test_differential(gpu):
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     mx = _model(gpu)
     ty = _tree(gpu)
     sy = GpuServer(ty, 1024, 1 << 21)
@@ -654,7 +654,7 @@ def test_bad_tables(gpu):
 # ---- 7. the session table ---------------------------------------------------
 
 def test_session_table(gpu):
-    from zkmi.bench.synthetic import GpuSessionTable
+    from zkmi.server.sessions import GpuSessionTable
     m = _model(gpu)
     tab = GpuSessionTable(m.tree, cap=64)
     sid = [tab.sid_of(k) for k in range(5)]
@@ -698,7 +698,8 @@ def test_session_table(gpu):
 # ---- 8. the interface -------------------------------------------------------
 
 def test_interface_refusals(gpu):
-    from zkmi.bench.synthetic import GpuServer, GpuTree, SessionSegments
+    from zkmi.server.engine import GpuServer, SessionSegments
+    from zkmi.server.tree import GpuTree
     tree = _tree(gpu)
     rx = dev_bytes(_stream([dict(get(leaf(1)), xid=1)]), gpu)
     segs = _segments(gpu, [0, rx.numel()], [0], [-1])
@@ -721,7 +722,7 @@ def test_interface_refusals(gpu):
 def test_wslots_out_of_range_arm_nothing(gpu):
     """wt_arm's rule (zk_tree.h): a watcher slot below 0 or above 63 arms
     nothing."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _tree(gpu)
     srv = GpuServer(tree, 64, 1 << 16)
     census = tree.watch_census()
@@ -812,7 +813,7 @@ def test_ops_check_their_tensors(gpu):
     with pytest.raises(RuntimeError):
         _lib.sess_group_workspace(0)
     # the serves: a table whose rows disagree, a short f_seg
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _tree(gpu)
     srv = GpuServer(tree, cap, 1 << 16)
     r = srv.resp
@@ -854,7 +855,8 @@ def test_segment_table_list_is_checked_once_for_all(gpu):
     """Every op of a session batch takes the segment table as one list,
     ``[f_seg, sessions, wslots, seg_state, bad]``, and refuses a malformed
     one before it launches anything: its outputs stay zero."""
-    from zkmi.bench.synthetic import GpuServer, GpuTree
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     L = _lib.lib()
     S, cap, ecap = 3, 256, 64
     tree = GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,

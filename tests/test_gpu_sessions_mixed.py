@@ -41,7 +41,8 @@ def _frozen_time(monkeypatch):
 
 
 def _server(gpu, fanout=10, frames=1024, acl=True, watch=True):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(LEAVES[fanout], 16, fanout=fanout, device=gpu, spare=4.0,
                    ctime_ms=int(NOW * 1000), acl_cap=512 if acl else 0,
                    watch_cap=2048 if watch else 0)
@@ -387,7 +388,7 @@ def test_bad_tables_refuse_every_engine(gpu):
 
 
 def test_dead_session_refuses_its_segment(gpu):
-    from zkmi.bench.synthetic import GpuSessionTable
+    from zkmi.server.sessions import GpuSessionTable
     srv = _server(gpu)
     tree = srv.tree
     tab = GpuSessionTable(tree, cap=64)
@@ -528,7 +529,7 @@ class MixSessModel(SessModel):
 
 
 def test_model_churn(gpu):
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _tree(gpu, acl_cap=512)
     m = MixSessModel(tree, GpuServer(tree, 1024, 1 << 21), gpu)
     rng = random.Random(31)
@@ -670,7 +671,8 @@ def test_empty_batch_with_terminator(gpu):
 
 
 def test_interface_refusals(gpu):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     rx = torch.zeros(64, dtype=U8, device=gpu)
     segs = _segments(gpu, [0, 0], [0], [-1])
     tree = GpuTree(100, 16, fanout=10, device=gpu)

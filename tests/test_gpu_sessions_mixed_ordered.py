@@ -31,7 +31,8 @@ def _frozen_time(monkeypatch):
 
 
 def _server(gpu, acl=False, frames=1024):
-    from zkmi.bench.synthetic import GpuServer, GpuTree
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,
                    watch_cap=4096, scratch=1 << 20,
                    ctime_ms=int(NOW * 1000), acl_cap=512 if acl else 0)
@@ -229,7 +230,7 @@ def test_chains_with_lists_against_the_model(gpu):
 # ---- (c) deferral ------------------------------------------------------------
 
 def test_deferral(gpu):
-    from zkmi.bench.synthetic import OrderDefer
+    from zkmi.server.engine import OrderDefer
     srv = _server(gpu)
     m = TreeModel(srv.tree, srv, gpu)
     hot, other = leaf(3), leaf(FANOUT + 4)
@@ -310,7 +311,7 @@ def test_deferred_sequential_create_keeps_its_number(gpu):
     the served frames in batch order and bumps the parent's cversion where
     the deferred numbered create stood; names, Stats and the parent's
     cversion / numChildren agree over both batches."""
-    from zkmi.bench.synthetic import OrderDefer
+    from zkmi.server.engine import OrderDefer
     srv = _server(gpu)
     m = TreeModel(srv.tree, srv, gpu)
     hot, d = leaf(3), dirp(5)
@@ -374,7 +375,7 @@ def test_defer_none_refuses_as_the_library(gpu):
     reps, _, _ = _serve(srv, gpu, conns, ordered=True, passes=4)
     assert [rs[0]['err'] for rs in reps] == ['OK'] * 4 + ['SYSTEM_ERROR'] * 2
     with pytest.raises(ValueError):
-        from zkmi.bench.synthetic import OrderDefer
+        from zkmi.server.engine import OrderDefer
         _serve(srv, gpu, conns, defer=OrderDefer(6, gpu))
 
 
@@ -383,7 +384,8 @@ def test_defer_none_refuses_as_the_library(gpu):
 def test_deferred_frames_have_no_effect(gpu):
     """Behind an overflowing set on their connections: a CLOSE_SESSION closes
     nothing, a watch=1 list arms nothing, a SET_WATCHES catches nothing up."""
-    from zkmi.bench.synthetic import GpuSessionTable, OrderDefer
+    from zkmi.server.engine import OrderDefer
+    from zkmi.server.sessions import GpuSessionTable
     srv = _server(gpu)
     hot, d = leaf(3), dirp(5)
     S = 7

@@ -211,7 +211,8 @@ class ResumeModel(SessModel):
 
 
 def _model(gpu, frames=1024, watch_cap=4096):
-    from zkmi.bench.synthetic import GpuServer, GpuTree
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,
                    watch_cap=watch_cap, scratch=1 << 20)
     srv = GpuServer(tree, frames, 1 << 21)
@@ -491,7 +492,7 @@ def _single_events(srv):
 
 def _twin(gpu, before, **kw):
     """Two trees and servers in the same state after the writes ``before``."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     out = []
     for _ in range(2):
         tree = _tree(gpu, **kw)
@@ -637,7 +638,7 @@ def _census_after(m, segs, **kw):
 
 
 def test_refusals(gpu):
-    from zkmi.bench.synthetic import GpuSessionTable
+    from zkmi.server.sessions import GpuSessionTable
     m = _model(gpu)
     tab = GpuSessionTable(m.tree, cap=64)
     sid = [tab.sid_of(k) for k in range(3)]
@@ -689,7 +690,7 @@ def test_mixed(gpu):
     around the SET_WATCHES frames: the replies of the call without resume,
     the catch-up of serve_sessions(resume=True) on the SET_WATCHES frames
     alone."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     before, data, exist, child, after = _plain_world()
     rel = 2030
     trees = []
@@ -767,7 +768,8 @@ def test_default_is_unchanged(gpu):
     """Without ``resume`` a SET_WATCHES frame gets its header-only reply and
     nothing else, from both entry points; ``resume_notif`` is not written;
     ``resume=True`` without a watch table raises."""
-    from zkmi.bench.synthetic import GpuServer, GpuTree
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     m = _model(gpu)
     a = m.session(7)
     rel = m.mark()
@@ -844,7 +846,7 @@ def test_op_checks_its_tensors(gpu):
         call(ncap=0)
     with pytest.raises(RuntimeError):
         call(ncap=cap + 1)
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     plain = GpuTree(200, 16, fanout=FANOUT, device=gpu, seed=3)
     with pytest.raises(RuntimeError):
         _lib.watch_resume_sessions(

@@ -262,7 +262,7 @@ def test_fused_check_on_the_malformed_corpus(gpu, off):
     'negative' ones and the special xids do not), and against xids no reply
     carries.  Rows and count are the plain decoder's, the count the
     corpus's own."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     nodes = (11, 110, 16)
     c = M.ReplyCorpus(seed=4, n=600, nodes=nodes)
     t = B.XidTable(bits=M.XID_BITS, device=gpu)

@@ -23,7 +23,8 @@ WIN = 400               # windowed names, one scan shared by the tests
 
 def _tree(gpu, cap_frames=1024, **kw):
     """The smallest tree: 12 static nodes, 1024 spare, 4096 index entries."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0, **kw)
     # (the names below are chosen for this table size)
     assert (tree.cap, tree.hcap) == (1036, HCAP)
@@ -538,7 +539,8 @@ def test_ordered_churn(gpu):
     parents of their own (see _ordered_batch), so their names are compared
     in full.  The largest rank the ordering pass reports equals the host's
     (treemodel.host_ranks)."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0,
                    scratch=1 << 20)
     srv = GpuServer(tree, 512, 1 << 20)

@@ -66,7 +66,7 @@ def _replies(raw, pk):
 
 
 def _server(tree, frames=1024):
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     return GpuServer(tree, frames, 4 << 20)
 
 
@@ -75,7 +75,7 @@ def churned(gpu):
     """The source tree after its history, its image, and what the source
     answers for every path that ever lived (taken before anything else
     runs)."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(10, 2048, fanout=10, device=gpu, spare=6.0)
     assert 1100 <= tree.cap <= 1110
     m = TreeModel(tree, _server(tree), gpu)
@@ -171,7 +171,7 @@ def test_snapshot_after_churn(churned, gpu):
 # ---- 2. load and carry on ---------------------------------------------------
 
 def test_load_and_carry_on(churned, gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     c = churned
     m = c['model']
     t = GpuTree.load(c['img'], device=gpu, spare=0.5, hash_factor=4,
@@ -236,7 +236,7 @@ def _acl_create(path, acl):
 
 
 def test_acls_through_image(gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     src = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0, acl_cap=3)
     srv = _server(src)
     vec = [C.DIGEST_ACL,
@@ -324,7 +324,7 @@ def _host_db():
 
 
 def test_host_made_image(gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     db = _host_db()
     recs = [{'path': p, 'stat': n.stat, 'data': bytes(n.data or b''),
              'acl': n.acl} for p, n in sorted(db.nodes.items()) if p != '/']
@@ -351,7 +351,7 @@ def test_host_made_image(gpu):
 
 @pytest.mark.parametrize('n', [0, 1])
 def test_tiny_images(gpu, n):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     recs = [C.rec('/only', b'1', z=4)][:n]
     t = GpuTree.load(TI.pack(recs, 9), device=gpu)
     assert t.digest()[:2] == (TI.digest(recs), n)
@@ -370,7 +370,7 @@ def test_tiny_images(gpu, n):
 # ---- 5. the reject side -----------------------------------------------------
 
 def _load_outcome(img, gpu, **kw):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     try:
         GpuTree.load(img, device=gpu, **kw)
         out = (TI.OK, -1)
@@ -403,7 +403,7 @@ def test_colliding_keys_in_one_wave(gpu):
     indices: one wave inserts them, the second and third behind the first's
     unpublished entry (the index build's second launch).  They are no
     duplicates: the image loads and every one answers its own data."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     twins = C.twin_paths()
     assert len({_lib.acl_hash(p.encode()) for p in twins}) == 1
     img = dict((c[0], c[1]) for c in C.corpus())['twins3']
@@ -430,7 +430,7 @@ def test_lying_size_hints_stay_bounded(gpu):
     """The loader sizes the tree from the header before the device has
     checked anything: hints far past what the image can hold must not size
     the tree past a few times the image."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     img = dict((c[0], c[1]) for c in C.corpus())['hint-huge']
     t = GpuTree.load(img, device=gpu)
     assert t.slab_cap < (1 << 22) and t.path_cap < (1 << 22)
@@ -476,7 +476,7 @@ def test_snapshot_into_fixed_buffer(churned, gpu):
 # ---- 7. the ops' argument checks --------------------------------------------
 
 def test_op_argument_checks(gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     t = GpuTree(10, 16, fanout=10, device=gpu, spare=0.0)
     ops = _lib.lib()
     U8, I64 = torch.uint8, torch.int64

@@ -34,7 +34,8 @@ def dirp(d):
 
 
 def _model(gpu, frames=1024, watch_cap=4096):
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(NLEAF, 16, fanout=FANOUT, device=gpu, seed=3,
                    watch_cap=watch_cap, scratch=1 << 20)
     srv = GpuServer(tree, frames, 1 << 21)

@@ -52,7 +52,8 @@ class Mirror(object):
     """The GPU tree and the fake server's database side by side."""
 
     def __init__(self, dev):
-        from zkmi.bench.synthetic import GpuTree, GpuServer
+        from zkmi.server.engine import GpuServer
+        from zkmi.server.tree import GpuTree
         from zkmi.server.fakezk import ZKDatabase
         self.dev = dev
         self.tree = GpuTree(NLEAF, 24, fanout=FANOUT, device=dev, seed=3,

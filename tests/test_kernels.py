@@ -419,7 +419,7 @@ def test_decode_requests_matches_oracle(gpu):
 
 
 def _small_tree(gpu, n=5000, data=100, spare=0.25):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     return GpuTree(n, data, fanout=100, device=gpu, spare=spare)
 
 
@@ -483,7 +483,7 @@ def test_encode_responses_serve_mix_matches_oracle(gpu, dist, mix):
     of the writer
     (each aligned 16-byte chunk built from its record's slot) 2.4x slower
     than the LDS-staged one (README, Measured and rejected)."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.ops import batch as B
     tree = GpuTree(5000, 100, fanout=100, device=gpu, spare=0.25,
                    data_dist=dist)
@@ -728,7 +728,7 @@ def test_gpu_tree_mutations(gpu):
     """SET_DATA version CAS, CREATE (parent must exist, NODE_EXISTS),
     DELETE through the GPU server, checked reply by reply."""
     from zkmi.ops import batch as B
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _small_tree(gpu, 1000, 16)
     leaf = '/bench/d000000/n000000003'
     pk = [
@@ -817,7 +817,7 @@ def test_handshake_records_k9(gpu):
 def test_gpu_free_ring_recycles_nodes(gpu):
     """DELETE pushes the node on the free ring, the NEXT batch's CREATE pops
     it (same batch never does) and reuses its slot and path storage."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     from zkmi.ops import _lib
     tree = _small_tree(gpu, 1000, 16)
     srv = GpuServer(tree, 64, 1 << 16)
@@ -855,7 +855,7 @@ def test_gpu_ephemeral_sequential_and_expire(gpu):
     sent them, as a ZooKeeper leader names them —, EPHEMERAL records the
     session, children of ephemerals are refused, and expiring the session
     removes exactly its ephemerals."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _small_tree(gpu, 1000, 16)
     srv = GpuServer(tree, 64, 1 << 16)
     E = ['EPHEMERAL']
@@ -919,7 +919,7 @@ def test_gpu_sequential_names_in_stream_order(gpu, n, nparents):
     for one pipelined session.  The parent's cversion moves by the count;
     a second batch continues after it.  (reference test/basic.test.js:
     550-611; a ZooKeeper leader names them in zxid order.)"""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _small_tree(gpu, 1000 * 10, 16, spare=1.0)
     srv = GpuServer(tree, 4096, 1 << 22)
     parents = ['/bench/d%06d' % (d % 10) for d in range(nparents)]
@@ -961,7 +961,7 @@ def test_gpu_sequential_replicas_agree(gpu):
     same znodes, names, zxids, owners and data (GpuTree.digest), whatever
     order their waves ran in; a failed SEQUENTIAL create leaves a gap (its
     number is not reused), and the next batch numbers after it."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     trees = [_small_tree(gpu, 4000, 16, spare=2.0) for _ in range(2)]
     srvs = [GpuServer(t, 4096, 1 << 22) for t in trees]
     parents = ['/bench/d%06d' % d for d in range(40)]
@@ -998,7 +998,7 @@ def test_gpu_expiry_reclaims_tombstones(gpu):
     continues a probe chain (zk_tree.h ht_reclaim), and the next batch's
     names take over the tombstones their probes pass (tree_insert<true>),
     so the tombstone count settles instead of growing until a rebuild."""
-    from zkmi.bench.synthetic import GpuServer
+    from zkmi.server.engine import GpuServer
     tree = _small_tree(gpu, 4000, 16, spare=1.5)
     srv = GpuServer(tree, 4096, 1 << 22)
     parents = ['/bench/d%06d' % d for d in range(40)]
@@ -1120,7 +1120,7 @@ def test_gpu_session_handshake_k9_server(gpu):
     """The GPU server's handshake against the oracle's records: new
     session, resume with the right password, wrong password and unknown id
     get the expired answer, a too-new lastZxidSeen is refused."""
-    from zkmi.bench.synthetic import GpuSessionTable
+    from zkmi.server.sessions import GpuSessionTable
     from zkmi.ops import _lib
     tree = _small_tree(gpu, 1000, 16)
     st = GpuSessionTable(tree)
@@ -1161,7 +1161,8 @@ def test_gpu_watch_pipeline_single_rank(gpu):
     arms the server's watch table, SET_DATA of the same nodes fires one
     NodeDataChanged each (K13), K1 + K8 decode and the device check; a few
     records against the Jute oracle, and nothing fires twice."""
-    from zkmi.bench.synthetic import GpuTree, WatchPipeline
+    from zkmi.bench.synthetic import WatchPipeline
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(20000, 37, fanout=100, device=gpu, seed=0,
                    watch_cap=8192)
     pipe = WatchPipeline(tree, 5000)
@@ -1196,7 +1197,8 @@ def _watch_rank(rank, world, port, q):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
-        from zkmi.bench.synthetic import GpuTree, WatchPipeline
+        from zkmi.bench.synthetic import WatchPipeline
+        from zkmi.server.tree import GpuTree
         dev = torch.device('cuda', 0)
         tree = GpuTree(20000, 37, fanout=100, device=dev, seed=rank,
                        watch_cap=8192)
@@ -1236,7 +1238,8 @@ def test_gpu_get_pipeline_variable_sizes(gpu):
     host framer's.  (Structured reply bytes keep garbage chains alive deep
     into K1's tiles; a join past the first 2 KiB of a tile once took the
     wrong survivor index.)"""
-    from zkmi.bench.synthetic import GpuTree, GetPipeline
+    from zkmi.bench.synthetic import GetPipeline
+    from zkmi.server.tree import GpuTree
     tree = GpuTree(100_000, 0, fanout=1000, device=gpu, data_dist=(0, 1024),
                    name_pad=(0, 16))
     pipe = GetPipeline(tree, 1 << 16)

@@ -115,7 +115,8 @@ def _random_batch(rng, paths, n, xid0=0):
 
 @pytest.mark.gpu
 def test_ordered_batch_matches_sequential_server():
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     dev = torch.device('cuda', 0)
     tree = GpuTree(1000, 16, fanout=100, device=dev, spare=0.5,
                    scratch=1 << 20)
@@ -147,7 +148,8 @@ def test_ordered_batch_matches_sequential_server():
 @pytest.mark.gpu
 def test_ordered_create_set_delete_create_chain():
     """The canonical chain on one path, with reads between every step."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     dev = torch.device('cuda', 0)
     tree = GpuTree(1000, 16, fanout=100, device=dev, scratch=1 << 16)
     srv = GpuServer(tree, 64, 1 << 16)
@@ -189,7 +191,8 @@ def test_ordered_create_set_delete_create_chain():
 def test_ordered_excess_rank_is_refused():
     """More same-path requests than passes: the excess is answered
     SYSTEMERROR and order_stats reports the rank; nothing is misordered."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     dev = torch.device('cuda', 0)
     tree = GpuTree(1000, 16, fanout=100, device=dev, scratch=1 << 16)
     srv = GpuServer(tree, 64, 1 << 16)
@@ -208,7 +211,8 @@ def test_ordered_excess_rank_is_refused():
 def test_ordered_read_only_and_unrelated_paths_single_rank():
     """Paths only read, and SEQUENTIAL creates, are never ranked: a GET
     batch is served in one effective pass and all succeed."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     dev = torch.device('cuda', 0)
     tree = GpuTree(1000, 16, fanout=100, device=dev)
     srv = GpuServer(tree, 256, 1 << 17)
@@ -228,7 +232,8 @@ def test_ordered_read_only_and_unrelated_paths_single_rank():
 def test_chain_pipeline_steps():
     """bench --workload chain: every path's create -> set -> get -> delete
     in one batch, checked on the device; the node count stays steady."""
-    from zkmi.bench.synthetic import GpuTree, ChainPipeline
+    from zkmi.bench.synthetic import ChainPipeline
+    from zkmi.server.tree import GpuTree
     from zkmi.ops import _lib
     dev = torch.device('cuda', 0)
     tree = GpuTree(20000, 37, fanout=100, device=dev, spare=1.0,
@@ -263,7 +268,8 @@ def test_ordered_parent_child_batch_matches_sequential_server():
     parent delete refused while it has a child — every reply as the
     sequential server gives it (a create and its parent's create conflict;
     a parent's Stat read conflicts with its children's writes)."""
-    from zkmi.bench.synthetic import GpuTree, GpuServer
+    from zkmi.server.engine import GpuServer
+    from zkmi.server.tree import GpuTree
     dev = torch.device('cuda', 0)
     tree = GpuTree(1000, 16, fanout=100, device=dev, spare=0.5,
                    scratch=1 << 20)
@@ -316,7 +322,8 @@ def test_ordered_parent_child_batch_matches_sequential_server():
 def test_nest_pipeline_steps():
     """bench --workload nest: depth-3 creates, the parent's EXISTS and the
     bottom-up deletes of every tree in one batch, checked on the device."""
-    from zkmi.bench.synthetic import GpuTree, NestPipeline
+    from zkmi.bench.synthetic import NestPipeline
+    from zkmi.server.tree import GpuTree
     from zkmi.ops import _lib
     dev = torch.device('cuda', 0)
     tree = GpuTree(20000, 37, fanout=100, device=dev, spare=1.0,

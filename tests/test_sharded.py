@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_router_matches_host_hash(gpu):
     """route.hip's owners equal the host FNV-1a mirror; the split is stable
     and grouped by owner."""
-    from zkmi.bench.synthetic import GpuTree, path_owner
+    from zkmi.server.tree import GpuTree, path_owner
     from zkmi.parallel.sharded import ShardedGetPipeline
     tree = GpuTree(20000, 37, fanout=100, device=gpu, seed=0)
     pipe = ShardedGetPipeline(tree, 5000)
@@ -200,7 +200,7 @@ def test_seg_pack_unpack_inplace(gpu):
 
 
 def test_sharded_get_one_rank(gpu):
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.parallel.sharded import ShardedGetPipeline
     tree = GpuTree(20000, 37, fanout=100, device=gpu, seed=0, shard=(0, 1))
     for streams in (1, 2):
@@ -231,7 +231,8 @@ def _rank(rank, world, port, q, streams):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
-        from zkmi.bench.synthetic import GpuTree, GpuServer
+        from zkmi.server.engine import GpuServer
+        from zkmi.server.tree import GpuTree
         from zkmi.ops import batch as B
         from zkmi.parallel.sharded import ShardedGetPipeline
         dev = torch.device('cuda', 0)
@@ -310,7 +311,7 @@ def test_sharded_forced_route_rccl_captured(gpu, streams):
     K1 / K12 / K13 / K1 / K2-K4 around it), captured with its collectives
     as one HIP graph and replayed: every reply checks out on the device."""
     import torch.distributed as dist
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.parallel.sharded import ShardedGetPipeline
     s = socket.socket()
     s.bind(('127.0.0.1', 0))

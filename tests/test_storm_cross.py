@@ -36,7 +36,8 @@ def _rank(rank, world, port, q, steps, n):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
-        from zkmi.bench.synthetic import GpuTree, StormPipeline
+        from zkmi.bench.synthetic import StormPipeline
+        from zkmi.server.tree import GpuTree
         dev = torch.device('cuda', 0)
         # every member starts from the same tree (one replicated tree)
         tree = GpuTree(20000, 37, fanout=100, device=dev, seed=0,

@@ -96,7 +96,7 @@ def test_serve_outputs_checked(gpu):
     """The three serve ops check their ten output tensors through one
     helper (serve_out): a short list, a short tensor and a wrong dtype raise
     the same message from each, before any launch."""
-    from zkmi.bench.synthetic import GpuTree
+    from zkmi.server.tree import GpuTree
     from zkmi.ops import batch as B
     ops = _lib.lib()
     ncap = 4

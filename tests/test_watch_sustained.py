@@ -26,8 +26,9 @@ pytestmark = pytest.mark.gpu
 
 def test_watch_steps_do_not_stall(gpu):
     from zkmi.bench import synthetic as S
+    from zkmi.server.tree import GpuTree
     n = 1 << 20
-    tree = S.GpuTree(1000000, 100, device=gpu, seed=0, watch_cap=2 * n)
+    tree = GpuTree(1000000, 100, device=gpu, seed=0, watch_cap=2 * n)
     pipe = S.WatchPipeline(tree, n, seed=0)
     acc = torch.zeros(64, dtype=torch.int64, device=gpu)
     steps = 130

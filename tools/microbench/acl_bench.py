@@ -28,8 +28,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import consts  # noqa: E402
 from zkmi.ops import _lib  # noqa: E402
 from zkmi.ops import batch as B  # noqa: E402
-from zkmi.bench.synthetic import (GpuTree, GpuServer, AclPipeline,  # noqa: E402
-                                  MIX_ACLS, _acl_table, _arena)
+from zkmi.bench.synthetic import (AclPipeline, MIX_ACLS,  # noqa: E402
+                                  _acl_table, _arena)
+from zkmi.server.engine import GpuServer  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 SESSION = 0x5EED

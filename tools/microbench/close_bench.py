@@ -26,8 +26,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import jute  # noqa: E402
-from zkmi.bench.synthetic import (GpuServer, GpuTree,  # noqa: E402
-                                  SessionSegments)
+from zkmi.server.engine import GpuServer, SessionSegments  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 I64, I32 = torch.int64, torch.int32
 KS = (1, 16, 256, 4096)

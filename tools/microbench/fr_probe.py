@@ -12,7 +12,7 @@ import socket
 import torch
 import torch.distributed as dist
 
-from zkmi.bench.synthetic import GpuTree
+from zkmi.server.tree import GpuTree
 from zkmi.parallel.sharded import ShardedGetPipeline
 
 ap = argparse.ArgumentParser()

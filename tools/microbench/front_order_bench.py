@@ -26,8 +26,9 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import Client, jute  # noqa: E402
-from zkmi.bench.synthetic import (GpuServer, GpuTree, OrderDefer,  # noqa: E402
-                                  SessionSegments)
+from zkmi.server.engine import (GpuServer, OrderDefer,  # noqa: E402
+                                SessionSegments)
+from zkmi.server.tree import GpuTree  # noqa: E402
 from zkmi.server.gpu import GpuZKServer  # noqa: E402
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8

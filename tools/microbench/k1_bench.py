@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import codec, consts  # noqa: E402
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 from zkmi.ops import _lib  # noqa: E402
 from zkmi.ops import batch as B  # noqa: E402
 
@@ -147,13 +148,13 @@ def main():
     if a.data_dist:
         lo, hi = a.data_dist.split('-')
         dist = (int(lo), int(hi))
-    tree = S.GpuTree(1_000_000, 100, device=dev, seed=0, data_dist=dist)
+    tree = GpuTree(1_000_000, 100, device=dev, seed=0, data_dist=dist)
     if a.workload == 'mix':
-        tree = S.GpuTree(1_000_000, 100, device=dev, seed=0,
-                         spare=(2 * a.batch + 8192) / 1e6 + 0.05)
+        tree = GpuTree(1_000_000, 100, device=dev, seed=0,
+                       spare=(2 * a.batch + 8192) / 1e6 + 0.05)
     if a.workload == 'storm':
-        tree = S.GpuTree(1_000_000, 100, device=dev, seed=0, hash_factor=2,
-                         spare=(3 * a.batch + 8192) / 1e6 + 0.05)
+        tree = GpuTree(1_000_000, 100, device=dev, seed=0, hash_factor=2,
+                       spare=(3 * a.batch + 8192) / 1e6 + 0.05)
     if a.zxid is not None:
         tree.counters[_lib.TC_ZXID] = a.zxid
     if a.workload in ('mix', 'storm'):

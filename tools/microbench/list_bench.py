@@ -21,7 +21,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi.ops import _lib  # noqa: E402
-from zkmi.bench.synthetic import GpuTree, ListPipeline  # noqa: E402
+from zkmi.bench.synthetic import ListPipeline  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 
 def timed(fn, reps, warm=3):

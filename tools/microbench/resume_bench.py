@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
-from zkmi.bench.synthetic import (GpuServer, GpuTree,  # noqa: E402
-                                  SessionSegments)
+from zkmi.server.engine import GpuServer, SessionSegments  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 SHAPES = ((1024, 64), (8, 65536))

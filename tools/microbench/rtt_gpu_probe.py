@@ -45,8 +45,9 @@ def main():
         torch.ones(1, device='cuda').sum().item()
         stage('1_gpu_init')
         from zkmi.bench import synthetic as S
+        from zkmi.server.tree import GpuTree
         dev = torch.device('cuda', 0)
-        tree = S.GpuTree(1000000, 100, device=dev, seed=0)
+        tree = GpuTree(1000000, 100, device=dev, seed=0)
         pipe = S.GetPipeline(tree, 1 << 20, seed=0, streams=2)
         acc = torch.zeros(64, dtype=torch.int64, device=dev)
         for _ in range(3):

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(
 import torch  # noqa: E402
 
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 from zkmi.ops import _lib  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -30,8 +31,8 @@ ap.add_argument('--ndirs', type=int, default=1024)
 a = ap.parse_args()
 dev = torch.device('cuda', 0)
 spare = (a.batch * 3 + 8192) / a.nodes
-tree = S.GpuTree(a.nodes, 100, device=dev, seed=0, spare=spare + 0.05,
-                 hash_factor=2)
+tree = GpuTree(a.nodes, 100, device=dev, seed=0, spare=spare + 0.05,
+               hash_factor=2)
 pipe = S.StormPipeline(tree, a.batch, ndirs=a.ndirs)
 acc = torch.zeros(64, dtype=torch.int64, device=dev)
 pipe.step(acc=acc)

@@ -26,8 +26,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import consts  # noqa: E402
-from zkmi.bench.synthetic import (GpuServer, GpuTree,  # noqa: E402
-                                  SessionSegments)
+from zkmi.server.engine import GpuServer, SessionSegments  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 SHAPES = ((64, 16), (1024, 16), (4096, 4), (8, 65536))

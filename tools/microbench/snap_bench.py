@@ -26,7 +26,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi.ops import _lib  # noqa: E402
-from zkmi.bench.synthetic import GpuTree, MixPipeline  # noqa: E402
+from zkmi.bench.synthetic import MixPipeline  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 from zkmi.utils import treeimage as TI  # noqa: E402
 
 I64, U8 = torch.int64, torch.uint8

@@ -10,7 +10,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from zkmi.bench.synthetic import GpuTree, StormPipeline  # noqa: E402
+from zkmi.bench.synthetic import StormPipeline  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 M64 = (1 << 64) - 1
 

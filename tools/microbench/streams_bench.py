@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 
 def run(tree, batch, streams, steps=20, warmup=3):
@@ -29,7 +30,7 @@ def run(tree, batch, streams, steps=20, warmup=3):
 
 def main():
     dev = torch.device('cuda', 0)
-    tree = S.GpuTree(1_000_000, 100, device=dev, seed=0)
+    tree = GpuTree(1_000_000, 100, device=dev, seed=0)
     batch = int(os.environ.get('BATCH', 1 << 20))
     for k in [int(x) for x in os.environ.get('STREAMS', '1,2,3,4').split(',')]:
         dt = run(tree, batch, k)

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(
 import torch  # noqa: E402
 
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--workload', default='mix')
@@ -35,14 +36,14 @@ a = ap.parse_args()
 dev = torch.device('cuda', 0)
 w = a.workload
 if w == 'watch':
-    tree = S.GpuTree(a.nodes, 100, device=dev, seed=0, watch_cap=2 * a.batch)
+    tree = GpuTree(a.nodes, 100, device=dev, seed=0, watch_cap=2 * a.batch)
     pipe = S.WatchPipeline(tree, a.batch, seed=0)
 else:
     spare = (a.batch + 8192) / a.nodes
     scratch = (a.batch // 2 + 64) * (80 + 112) if w in ('chain', 'nest') else 0
-    tree = S.GpuTree(a.nodes, 100, device=dev, seed=0, spare=spare + 0.05,
-                     scratch=scratch, hash_factor=a.hash_factor,
-                     compact_free=not a.no_compact)
+    tree = GpuTree(a.nodes, 100, device=dev, seed=0, spare=spare + 0.05,
+                   scratch=scratch, hash_factor=a.hash_factor,
+                   compact_free=not a.no_compact)
     pipe = {'mix': lambda: S.MixPipeline(tree, a.batch, 100, seed=0),
             'nest': lambda: S.NestPipeline(tree, a.batch, seed=0),
             'chain': lambda: S.ChainPipeline(tree, a.batch, 100, seed=0)}[w]()

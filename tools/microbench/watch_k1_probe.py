@@ -18,13 +18,14 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--steps', type=int, default=120)
 a = ap.parse_args()
 dev = torch.device('cuda', 0)
 n = 1 << 20
-tree = S.GpuTree(1000000, 100, device=dev, seed=0, watch_cap=2 * n)
+tree = GpuTree(1000000, 100, device=dev, seed=0, watch_cap=2 * n)
 pipe = S.WatchPipeline(tree, n, seed=0)
 acc = torch.zeros(64, dtype=torch.int64, device=dev)
 pipe.nscan.chain_stats()

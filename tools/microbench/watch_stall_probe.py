@@ -20,6 +20,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 from zkmi.ops import _lib  # noqa: E402
 
 
@@ -71,7 +72,7 @@ def main():
     gc.callbacks.append(on_gc)
     dev = torch.device('cuda', 0)
     n = 1 << 20
-    tree = S.GpuTree(1000000, 100, device=dev, seed=0, watch_cap=2 * n)
+    tree = GpuTree(1000000, 100, device=dev, seed=0, watch_cap=2 * n)
     pipe = S.WatchPipeline(tree, n, seed=a.seed)
     if a.prelaunch:
         x = torch.zeros(1, device=dev)

@@ -11,11 +11,12 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from zkmi.bench import synthetic as S  # noqa: E402
+from zkmi.server.tree import GpuTree  # noqa: E402
 
 
 def run(ndirs, batch=1 << 20, steps=10):
-    tree = S.GpuTree(1_000_000, 100, spare=(batch + 8192) / 1e6 + 0.05 +
-                     ndirs / 1e6)
+    tree = GpuTree(1_000_000, 100, spare=(batch + 8192) / 1e6 + 0.05 +
+                   ndirs / 1e6)
     pipe = S.MixPipeline(tree, batch, 100, ndirs=ndirs)
     for _ in range(3):
         pipe.step()

@@ -757,7 +757,7 @@ def encode_responses(resp, store, out_cap, out=None, stream=None,
                      prescanned=False, rec_off=None):
     """K13: server-mode reply encode -> (bytes, rec_off, total, err).
     ``store``: the node store's tensors [slab, slot_off, data_len,
-    slot_cap] (:attr:`zkmi.bench.synthetic.GpuTree.store`).
+    slot_cap] (:attr:`zkmi.server.tree.GpuTree.store`).
     ``presized``: the (sizes, workspace) pair of :func:`response_workspace`
     already filled by the producer; the sizes pass is then skipped.
     ``total_err``: the (total, err) pair to write (default: new ones);

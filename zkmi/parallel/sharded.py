@@ -42,7 +42,7 @@ then the W > 1 step runs as is over a one-rank RCCL group (route ->
 seg_pack -> all_to_all_single -> seg_unpack on HBM tensors), which
 executes and captures the multi-rank code path on one GPU.
 
-Each rank's :class:`~zkmi.bench.synthetic.GpuTree` indexes only its shard
+Each rank's :class:`~zkmi.server.tree.GpuTree` indexes only its shard
 (``shard=(rank, world)``): a read that reached the wrong rank would answer
 NO_NODE and fail the check.  ``coll_device='cpu'`` runs the all-to-alls on
 host tensors (a gloo rehearsal on ranks that share one GPU).
@@ -56,7 +56,8 @@ import torch.distributed as dist
 from .. import consts
 from ..ops import _lib
 from ..ops import batch as B
-from ..bench.synthetic import _GET_SRV_GROUP, _i64
+from ..bench.synthetic import _GET_SRV_GROUP
+from ..server.tree import _i64
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 
@@ -268,7 +269,7 @@ class _Conn(object):
     request / reply buffers, xid table, GPU server and slots."""
 
     def __init__(self, pipe, n, seed):
-        from ..bench.synthetic import GpuServer
+        from ..server.engine import GpuServer
         self.p = pipe
         t = pipe.tree
         W = pipe.world

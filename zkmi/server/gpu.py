@@ -1,6 +1,6 @@
 """A TCP front end for the GPU server: :class:`GpuZKServer` gives
 :class:`zkmi.Client` a ZooKeeper endpoint backed by the HBM tree
-(:class:`zkmi.bench.synthetic.GpuTree`).
+(:class:`zkmi.server.tree.GpuTree`).
 
 It is an in-process server, as :class:`FakeZKServer` is, on a thread of its
 own with a HIP stream of its own and non-blocking sockets on ``selectors``.
@@ -65,9 +65,9 @@ import numpy as np
 import torch
 
 from .. import consts
-from ..bench.synthetic import (GpuServer, GpuSessionTable, OrderDefer,
-                               SessionSegments)
 from ..ops import _lib
+from .engine import GpuServer, OrderDefer, SessionSegments
+from .sessions import GpuSessionTable
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
 SLOTS = 64

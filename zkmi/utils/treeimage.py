@@ -1,7 +1,7 @@
 """The GPU tree's image (version 1) on the host: build, read and check one
 without a GPU.  The layout is csrc/kernels/zk_snap.h's, which this module
-mirrors; :meth:`zkmi.bench.synthetic.GpuTree.snapshot` writes such an image
-on the device and :meth:`~zkmi.bench.synthetic.GpuTree.load` reads one.
+mirrors; :meth:`zkmi.server.tree.GpuTree.snapshot` writes such an image
+on the device and :meth:`~zkmi.server.tree.GpuTree.load` reads one.
 
 A record is a dict ``{'path': str, 'stat': jute.Stat, 'data': bytes,
 'acl': [ACL entries] or None}`` (``None``: the node's ACL binding was lost,
