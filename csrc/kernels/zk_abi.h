@@ -567,6 +567,21 @@ int zk_close_sessions(const ZkTree*, const int64_t*, const int32_t*, int64_t,
                       int64_t, int64_t, int64_t, const ZkSessionTable*,
                       int64_t, int64_t*, unsigned long long*, int64_t*,
                       hipStream_t);
+// ACL enforcement around a session batch of any op mix (tree_aclperm.hip; the
+// rule: zk_aclperm.h).  zk_aclperm_check, after zk_sess_assign and before the
+// split: (tree, ACL table, rx — written —, its length, frames off / len,
+// count, ncap, the whole batch's segment table, addrs[S]: each segment's peer
+// IPv4 address in host order, 0 none) -> deny[ncap], the denied frames' opcode
+// words in rx overwritten, stats[8] += (checked, denied, denied for a lost
+// binding).  zk_aclperm_fix, between the serve and its reply encode: (deny,
+// the split's cls / sub, the whole batch's count, ncap) -> the serve's r_err
+// of a denied frame NO_AUTH, stats[3] += the replies so answered.
+int zk_aclperm_check(const ZkTree*, const ZkAclTable*, uint8_t*, int64_t,
+                     const int64_t*, const int32_t*, const int64_t*, int64_t,
+                     const ZkSegs*, const int32_t*, int32_t*, int64_t*,
+                     hipStream_t);
+int zk_aclperm_fix(const int32_t*, const int32_t*, const int32_t*,
+                   const int64_t*, int64_t, int32_t*, int64_t*, hipStream_t);
 // The front end's I/O staging (front.hip; the rules: zk_front.h).
 // zk_front_chunk: bytes of the cut's staged window.  zk_front_cut: (raw, n,
 // raw_starts[S + 1], S, quota, max_packet) -> take[S], nfr[S], flag[S],

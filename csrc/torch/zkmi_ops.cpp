@@ -1976,6 +1976,53 @@ void close_frames(const std::vector<Tensor>& t, const Tensor& rx,
          "close_frames");
 }
 
+// ACL enforcement around a session batch of any op mix (tree_aclperm.hip).
+// The check: the whole batch's frames and segment table (segs()) against the
+// tree's ACLs for the peers addrs [S] -> deny [ncap], the denied frames'
+// opcode words in rx, stats [8] (accumulated).
+void aclperm_check(const std::vector<Tensor>& t,
+                   const std::vector<Tensor>& acl, const Tensor& rx,
+                   const Tensor& foff, const Tensor& flen, const Tensor& n_dev,
+                   int64_t ncap, const std::vector<Tensor>& sg,
+                   const Tensor& addrs, const Tensor& deny,
+                   const Tensor& stats) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a = acl_table(acl, d);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: aclperm_check ncap");
+  const ZkSegs m = segs(sg, ncap, d);
+  TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+              " elements, needs ", s.store.cap);
+  TORCH_CHECK(addrs.numel() == m.S, "zkmi: addrs has ", addrs.numel(),
+              " entries, sessions ", m.S);
+  hip_ok(zk_aclperm_check(
+             &s, &a, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m,
+             P<int32_t>(addrs, I32, m.S, "addrs", d),
+             P<int32_t>(deny, I32, ncap, "deny", d),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "aclperm_check");
+}
+
+// The fix-up between the serve and its reply encode: a denied frame of the
+// serve's class (the split's cls / sub over the whole batch's count) whose
+// reply the serve left BAD_ARGUMENTS -> NO_AUTH in r_err, counted in stats[3].
+void aclperm_fix(const Tensor& deny, const Tensor& cls, const Tensor& sub,
+                 const Tensor& n_dev, int64_t ncap, const Tensor& r_err,
+                 const Tensor& stats) {
+  const Tensor* d = &deny;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: aclperm_fix ncap");
+  hip_ok(zk_aclperm_fix(P<int32_t>(deny, I32, ncap, "deny"),
+                        P<int32_t>(cls, I32, ncap, "cls", d),
+                        P<int32_t>(sub, I32, ncap, "sub", d),
+                        P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+                        P<int32_t>(r_err, I32, ncap, "r_err", d),
+                        P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "aclperm_fix");
+}
+
 // Passes 2-7.  sids given: the direct form, K = its length (wslots, when
 // given, as long); else the list close_frames left in ws.  S: the sessions
 // the workspace was sized for (K <= S; removed has room for S).
@@ -2397,6 +2444,12 @@ TORCH_LIBRARY(zkmi, m) {
         "int S, int cap_frames, Tensor(b!)[] table, int server_id, int span, "
         "Tensor(c!) ws, Tensor(d!) removed, Tensor(e!) stats) -> ()",
         &close_sessions);
+  m.def("aclperm_check(Tensor[] tree, Tensor[] acl, Tensor(a!) rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor[] segs, Tensor addrs, Tensor(b!) deny, Tensor(c!) stats) "
+        "-> ()", &aclperm_check);
+  m.def("aclperm_fix(Tensor deny, Tensor cls, Tensor sub, Tensor count, "
+        "int ncap, Tensor(a!) r_err, Tensor(b!) stats) -> ()", &aclperm_fix);
   m.def("front_chunk() -> int", &front_chunk);
   m.def("front_cut(Tensor raw, int n, Tensor raw_starts, int quota, "
         "int max_packet, Tensor(a!) take, Tensor(b!) nfr, Tensor(c!) flag, "

@@ -21,7 +21,15 @@ events, median after warm-up replays):
 All three produce the same number of reply bytes (checked; the order of the
 names inside a list reply is the sweep's).  The SET_DATAs write the same
 bytes every replay, so the graphs replay on an unchanged tree.
-``--side`` times one side alone (a kernel trace of it)."""
+``--side`` times one side alone (a kernel trace of it).
+
+``--enforce-acl``: the sessions_mixed side serves with ``perms=`` (an address
+a connection; csrc/kernels/tree_aclperm.hip), the other sides as ever.  On the
+tree as built every node carries the open ACL: the check's fast path.
+``--acl-vector`` first binds every node to one three-entry vector whose last
+entry grants (a digest entry, an ip entry of another network, world:anyone):
+every check walks the arena's bytes; nothing is denied either way, so all
+sides still produce the same reply bytes."""
 
 import argparse
 import os
@@ -35,7 +43,9 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
 from zkmi import consts  # noqa: E402
-from zkmi.server.engine import GpuServer, SessionSegments  # noqa: E402
+from zkmi.ops import _lib  # noqa: E402
+from zkmi.server.engine import (AclIdentity, GpuServer,  # noqa: E402
+                                SessionSegments)
 from zkmi.server.tree import GpuTree  # noqa: E402
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
@@ -96,6 +106,24 @@ def connection(rng, r, nodes, fanout, data):
     return b''.join(out), lists
 
 
+def bind_vector(tree):
+    """Every node's ACL word -> one three-entry vector, its bytes put on
+    the store's arena top (the intern index is not told: no CREATE of the
+    benchmark carries it)."""
+    def entry(perms, scheme, ident):
+        return struct.pack('>ii', perms, len(scheme)) + scheme + \
+            struct.pack('>i', len(ident)) + ident
+    vec = struct.pack('>i', 3) + entry(31, b'digest', b'bench:kQq8nOxk1N') \
+        + entry(31, b'ip', b'10.9.0.0/16') + entry(31, b'world', b'anyone')
+    node_acl, arena, _, _, ctr = tree.acl
+    top = int(ctr[_lib.AC_TOP].item())
+    assert top + len(vec) <= arena.numel()
+    arena[top:top + len(vec)] = dev_bytes(vec, arena.device)
+    ctr[_lib.AC_TOP] = top + len(vec)
+    ctr[_lib.AC_OLD_TOP] = top + len(vec)
+    node_acl.fill_((top << 24) | len(vec))
+
+
 def dev_bytes(raw, dev):
     return torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
 
@@ -116,7 +144,13 @@ def shape(tree, S, r, a, dev):
                            torch.tensor(slots, dtype=I32, device=dev))
     out_cap = S * r * 256 + sum(c[1] for c in conns) * per_list + (1 << 16)
     one = GpuServer(tree, S * r, out_cap, seq_order=False)
-    _, total, err, ft = one.serve_sessions_mixed(rx, n, segs)
+    perms = None
+    if a.enforce_acl:
+        # 10.1.x.y, a connection an address
+        perms = AclIdentity(torch.tensor(
+            [0x0A010000 + (s & 0xFFFF) for s in range(S)], dtype=I32,
+            device=dev))
+    _, total, err, ft = one.serve_sessions_mixed(rx, n, segs, perms=perms)
     torch.cuda.synchronize()
     T = int(total.item())
     st = one.session_stats()
@@ -126,9 +160,13 @@ def shape(tree, S, r, a, dev):
         S, r, S * r, T / 1e6)
     res = {}
     if a.side in ('all', 'new'):
-        g = graph_of(lambda: one.serve_sessions_mixed(rx, n, segs))
+        g = graph_of(lambda: one.serve_sessions_mixed(rx, n, segs,
+                                                      perms=perms))
         res['sessions_mixed'] = timed(g.replay, a.reps)
         del g
+        if perms is not None:
+            st = one.acl_enforce_stats()
+            assert st['denied'] == 0 and st['checked'] > 0, st
     if a.side in ('all', 'floor'):
         _, total, err, _ = one.serve_mixed(rx, n, session=sids[0],
                                            wslot=slots[0])
@@ -185,6 +223,10 @@ def main():
                         '%dx%d' % s for s in SHAPES))
     ap.add_argument('--side', default='all',
                     choices=('all', 'new', 'floor', 'serves'))
+    ap.add_argument('--enforce-acl', action='store_true',
+                    help='serve the sessions_mixed side with perms=')
+    ap.add_argument('--acl-vector', action='store_true',
+                    help='every node carries a three-entry ACL vector')
     a = ap.parse_args()
     shapes = SHAPES if not a.shape else \
         [tuple(int(x) for x in s.split('x')) for s in a.shape]
@@ -195,6 +237,13 @@ def main():
           'GET_CHILDREN2, ~10 %% GET_ACL, the rest 80 %% GET_DATA / 20 %% '
           'SET_DATA; captured graphs, median of %d' % (
               a.nodes, a.fanout, a.reps), flush=True)
+    if a.acl_vector:
+        bind_vector(tree)
+    if a.enforce_acl or a.acl_vector:
+        print('enforce-acl %s, %s' % (
+            'on' if a.enforce_acl else 'off',
+            'a three-entry vector a node' if a.acl_vector else
+            'the open ACL everywhere'), flush=True)
     for S, r in shapes:
         shape(tree, S, r, a, dev)
     return 0

@@ -490,6 +490,36 @@ def close_sessions(tree, sids, wslots, S, cap_frames, ws, removed, stats,
                          removed, stats)
 
 
+# ACL enforcement around a session batch of any op mix
+# (csrc/kernels/tree_aclperm.hip; the rule: zk_aclperm.h).  What
+# GpuServer.acl_enforce_stats reports, in order (stats[0..2])
+ACLPERM_STATS = ('checked', 'denied', 'denied_lost')
+
+
+def aclperm_check(tree, acl, rx, frame_off, frame_len, count, ncap, segs,
+                  addrs, deny, stats):
+    """After :func:`sess_assign` and before :func:`tree_mix_split`, on the
+    current stream: every frame of the whole batch's frame table whose
+    segment is served (``segs``: the whole batch's table), whose body parses
+    and whose target exists is checked against the target's ACL in ``acl``
+    for its segment's peer ``addrs[f_seg[i]]`` (int32 [S]: the IPv4 address
+    as a host-order word, 0 none).  ``deny`` (int32 [ncap]) is written for
+    the batch's frames; a denied frame's opcode word in ``rx`` is overwritten
+    with an opcode of no request.  ``stats`` (int64 [8]) accumulates
+    :data:`ACLPERM_STATS`.  One launch, no host read."""
+    lib().aclperm_check(tree, list(acl), rx, frame_off, frame_len, count,
+                        int(ncap), list(segs), addrs, deny, stats)
+
+
+def aclperm_fix(deny, cls, sub, count, ncap, r_err, stats):
+    """Between the serve of a session batch's serve class and its reply
+    encode: a frame :func:`aclperm_check` denied (``deny``; ``cls`` / ``sub``
+    / ``count``: :func:`tree_mix_split`'s over the whole batch) whose reply
+    the serve left BAD_ARGUMENTS is answered NO_AUTH in ``r_err`` and counted
+    in ``stats[3]``.  One launch, no host read."""
+    lib().aclperm_fix(deny, cls, sub, count, int(ncap), r_err, stats)
+
+
 # the front end's TX streams, in the order a connection's pieces are sent
 # (csrc/kernels/zk_front.h FS_*), and its assembly counters (FTS_*)
 FS_REPLY, FS_RESUME, FS_NOTIF, FS_CLOSE = range(4)

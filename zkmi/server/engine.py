@@ -42,6 +42,21 @@ class SessionSegments(object):
         self.S = S
 
 
+class AclIdentity(object):
+    """Who the connections of a session batch are, for the ACL check of
+    ``serve_sessions_mixed(perms=...)`` (the rule: csrc/kernels/
+    zk_aclperm.h): ``addrs``, a device int32 [S] tensor, segment s's peer
+    IPv4 address as a host-order 32-bit word (10.1.2.9 is ``0x0A010209``; a
+    value past 2^31 as its two's complement) or 0 for a peer without one,
+    which no ``ip`` entry matches."""
+
+    def __init__(self, addrs):
+        if addrs.dtype != I32 or addrs.dim() != 1 or addrs.numel() < 1:
+            raise ValueError('AclIdentity: addrs is an int32 [S] tensor')
+        self.addrs = addrs
+        self.S = int(addrs.numel())
+
+
 class OrderDefer(object):
     """Where ``serve_sessions_mixed(ordered=True, defer=...)`` leaves what it
     deferred, for a table of ``S`` segments; all device tensors, nothing is
@@ -263,6 +278,8 @@ class GpuServer(object):
         self.mix_flen = self.mix_counts = self.mix_frames = None
         self.mix_split_ws = self.mix_merge_ws = self.mix_rec_off = None
         self.mix_total_err = self.mix_scratch = self.mix_out = None
+        # the ACL check's verdicts and counters (lazy)
+        self.acl_deny = self.acl_enf = None
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -693,7 +710,7 @@ class GpuServer(object):
                          sg.state, sg.bad, **_table_args(table))
         out, rec_off, total, err = self._serve_class(
             rx, ft, sg.table(segs), segs, ordered, passes, None, close, None,
-            terminate)
+            terminate, None)
         self.last_rec_off = rec_off
         self.result = (out, total, err, ft)
         self._sessions_tail(rx, ft, segs, rec_off, total, err, table, resume,
@@ -701,14 +718,16 @@ class GpuServer(object):
         return self.result
 
     def _serve_class(self, rx, frames, seg_table, segs, ordered, passes,
-                     defer, close, rec_off, terminate):
+                     defer, close, rec_off, terminate, denied):
         """The serve of one class of a session batch's frames through to its
         reply encode: ``frames`` with their segment table ``seg_table``
         (:meth:`_SegState.table` of ``segs``) — the whole batch
         (:meth:`serve_sessions`) or the serve's class
         (:meth:`serve_sessions_mixed`).  ``defer``: the deferral's tables for
         ``tree_serve_ordered_sessions`` or None; ``rec_off``: where the
-        encode leaves the frame starts (None: its own).  Returns what
+        encode leaves the frame starts (None: its own); ``denied``: the
+        whole batch's frame count when the ACL check ran over it (its
+        fix-up goes between the serve and the encode) or None.  Returns what
         ``encode_responses`` returns."""
         L = _lib.lib()
         tree = self.tree
@@ -741,6 +760,9 @@ class GpuServer(object):
                                  self._acl_workspace())
         if close:
             self._close_frames(rx, frames, seg_table, segs.S)
+        if denied is not None:
+            _lib.aclperm_fix(self.acl_deny, self.mix_cls, self.mix_sub,
+                             denied, cap, r.err, self.acl_enf)
         enc = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
@@ -1161,7 +1183,7 @@ class GpuServer(object):
     def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
                              max_frame=None, out=None, resume=False,
                              close=False, ordered=False, passes=4,
-                             defer=None):
+                             defer=None, perms=None):
         """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
         connections of :class:`SessionSegments` ``segs``, whatever ops they
         mix, as ONE batch: :meth:`serve_sessions` for every op of
@@ -1257,6 +1279,40 @@ class GpuServer(object):
         batch whose table is unsound is refused as a whole and defers
         nothing.)
 
+        ``perms`` (an :class:`AclIdentity` of ``segs.S`` peers): the ACLs the
+        tree keeps are enforced (csrc/kernels/tree_aclperm.hip; the rule:
+        zk_aclperm.h).  None: every launch and every byte of the call are
+        what they are without the argument.  With it one launch after the
+        segment assign checks every frame whose segment is served, whose
+        body parses and whose target exists: GET_DATA and the list ops need
+        READ and SET_DATA WRITE on the node, CREATE needs CREATE on the
+        parent, DELETE needs DELETE on the parent and only when the node
+        itself exists; every other op needs nothing.  An entry grants when
+        it carries the bit and is ``world:anyone`` or an ``ip`` entry
+        (``a.b.c.d`` or ``a.b.c.d/bits``) that covers the segment's
+        address; every other scheme matches nobody.  The open ACL grants
+        without a read of the store; a node whose ACL found no room in it
+        (:meth:`acl_stats`) denies every op that needs a permission.  A
+        denied frame is answered NO_AUTH, header only, with its xid, and is
+        otherwise no request of the batch: it is looked up, claimed, armed,
+        fired, numbered (a denied SEQUENTIAL create takes no number), ranked
+        and deferred by nothing, under the unordered serve, ``ordered`` and
+        ``defer`` alike; a second launch, between the serve and its reply
+        encode, writes the code.  :meth:`acl_enforce_stats` reads the
+        counters.  Three points of the batch contract:
+
+        * permission and existence are those of the tree as the batch finds
+          it.  A node created in the batch is not protected before the next
+          batch — the moment its ACL is bound —, and a node deleted in it
+          still decides;
+        * NO_AUTH comes before NODE_EXISTS, BAD_VERSION and NOT_EMPTY and
+          after NO_NODE, as in ZooKeeper;
+        * the opcode words of the denied frames in the caller's ``rx`` are
+          overwritten (with an opcode of no request).
+
+        Raises ``ValueError`` on a tree without an ACL table and when
+        ``perms.addrs`` is not ``[segs.S]``.
+
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
         tree = self.tree
@@ -1277,6 +1333,13 @@ class GpuServer(object):
             if not isinstance(defer, OrderDefer) or defer.S != segs.S:
                 raise ValueError('serve_sessions_mixed: defer is an '
                                  'OrderDefer of segs.S segments')
+        if perms is not None:
+            if tree.acl is None:
+                raise ValueError('serve_sessions_mixed: perms needs a tree '
+                                 'with an ACL table (GpuTree(acl_cap=...))')
+            if not isinstance(perms, AclIdentity) or perms.S != segs.S:
+                raise ValueError('serve_sessions_mixed: perms is an '
+                                 'AclIdentity of segs.S addresses')
         self._mix_buffers()
         cap = self.cap_frames
         if self.seg is None or self.seg.S != segs.S:
@@ -1291,6 +1354,12 @@ class GpuServer(object):
         _lib.sess_assign(ft.off, ft.length, ft.count, cap, segs.starts,
                          segs.sessions, sg.f_seg, sg.first, sg.state, sg.bad,
                          **_table_args(table))
+        if perms is not None:
+            # (before the split: a denied frame is of the serve's class)
+            self._acl_enforce_buffers()
+            _lib.aclperm_check(tree.tensors, tree.acl, rx, ft.off, ft.length,
+                               ft.count, cap, sg.table(segs), perms.addrs,
+                               self.acl_deny, self.acl_enf)
         _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
                             tree.acl is not None, self.mix_cls, self.mix_sub,
                             self.mix_foff, self.mix_flen, self.mix_counts,
@@ -1304,7 +1373,8 @@ class GpuServer(object):
             defer.clipf, defer.deferred]
         a_out, _, a_total, a_err = self._serve_class(
             rx, fa, sg.table(segs, 0), segs, ordered, passes, clip, close,
-            self.mix_rec_off[0], False)
+            self.mix_rec_off[0], False,
+            ft.count if perms is not None else None)
         # the two read engines, after the batch's writes
         c_out, l_out = self.mix_scratch
         c_total, c_err = self.acl_total_err
@@ -1347,6 +1417,36 @@ class GpuServer(object):
         c = acl[4].cpu().tolist()
         return (c[_lib.AC_ENT], min(c[_lib.AC_TOP], acl[1].numel()),
                 c[_lib.AC_LOST])
+
+    def _acl_enforce_buffers(self):
+        """The ACL check's verdicts and counters, allocated on first use."""
+        if self.acl_deny is None:
+            dev = self.tree.device
+            self.acl_deny = torch.zeros(self.cap_frames, dtype=I32,
+                                        device=dev)
+            self.acl_enf = torch.zeros(8, dtype=I64, device=dev)
+
+    def acl_enforce_stats(self):
+        """What ``serve_sessions_mixed(perms=...)`` has decided since the
+        server was built (one host read): frames ``checked`` (a verdict was
+        reached: the segment served, the body parsed, the target there),
+        frames ``denied`` (answered NO_AUTH) and, of those, ``denied_lost``
+        (the target's ACL found no room in the store: closed).  All 0 on a
+        server that never enforced.  The counts are the check's: a denied
+        frame that ``defer`` takes out of its batch is checked, and counted,
+        again in the batch that serves it."""
+        if self.acl_enf is None:
+            return dict.fromkeys(_lib.ACLPERM_STATS, 0)
+        return dict(zip(_lib.ACLPERM_STATS, self.acl_enf.cpu().tolist()))
+
+    def acl_enforce_counters(self):
+        """The device counters :meth:`acl_enforce_stats` reads (int64 [8], in
+        ``_lib.ACLPERM_STATS`` order, then the replies answered NO_AUTH: a
+        deferred frame is not among them before it is served), for a caller
+        that folds them into a read of its own (the front end's report); no
+        host read."""
+        self._acl_enforce_buffers()
+        return self.acl_enf
 
     def _seq_order(self, rx, ft):
         """Number the batch's SEQUENTIAL creates in stream order (parent's

@@ -51,7 +51,13 @@ Known divergences from ZooKeeper:
 * 64 watcher slots: the 65th live session gets none, its watches arm nothing
   (``stats()['no_watcher_slot']``);
 * a batch whose reply encode overflowed has applied its writes and lost its
-  replies: its connections are dropped (``stats()['batches_lost']``).
+  replies: its connections are dropped (``stats()['batches_lost']``);
+* ``enforce_acl=True``: permission and existence are those of the tree as the
+  tick finds it (a node created in a tick is protected from the next one on);
+  only ``world`` and ``ip`` entries match anybody — there is no AUTH, so a
+  ``digest``, ``auth`` or ``sasl`` entry grants nothing, and no SET_ACL;
+  GET_ACL needs no permission (ZooKeeper 3.4 / 3.5); a node whose ACL found no
+  room in the store denies every op that needs a permission.
 """
 
 import heapq
@@ -66,7 +72,7 @@ import torch
 
 from .. import consts
 from ..ops import _lib
-from .engine import GpuServer, OrderDefer, SessionSegments
+from .engine import AclIdentity, GpuServer, OrderDefer, SessionSegments
 from .sessions import GpuSessionTable
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
@@ -108,6 +114,27 @@ class _Conn(object):
         self.dead = False
 
 
+def peer_ipv4(addr):
+    """The IPv4 address of a socket's peer (``accept()``'s or
+    ``getpeername()``'s address tuple) as a host-order 32-bit word in int32
+    range, the form :class:`AclIdentity` takes; for an IPv4-mapped IPv6 peer
+    the mapped address; 0 for anything else (which no ``ip`` ACL entry
+    matches)."""
+    try:
+        host = addr[0]
+        if ':' in host:
+            host = host.split('%', 1)[0]
+            raw = socket.inet_pton(socket.AF_INET6, host)
+            if raw[:12] != b'\0' * 10 + b'\xff\xff':
+                return 0
+            raw = raw[12:]
+        else:
+            raw = socket.inet_pton(socket.AF_INET, host)
+    except (OSError, TypeError, IndexError, ValueError, AttributeError):
+        return 0
+    return struct.unpack('>i', raw)[0]
+
+
 def _pinned(n, dtype, dev):
     t = torch.zeros(n, dtype=dtype)
     return t.pin_memory() if dev.type == 'cuda' else t
@@ -145,6 +172,15 @@ class GpuZKServer(object):
                     scratch tail (``GpuTree(scratch=...)``; ``ValueError``
                     without one) and ``cap_frames <= 65536``, and costs
                     about 3 ``P`` + 8 launches a tick more.
+    ``enforce_acl``  the ACLs the tree keeps are enforced (``GpuServer.
+                    serve_sessions_mixed(perms=...)``; the rule:
+                    csrc/kernels/zk_aclperm.h): a connection is its peer's
+                    IPv4 address, taken at ``accept`` (none for a peer that
+                    is not IPv4 or IPv4-mapped: no ``ip`` entry matches it),
+                    and a request its node's or parent's ACL does not allow
+                    is answered NO_AUTH.  It needs a tree with an ACL table
+                    (``ValueError`` without one) and costs two launches a
+                    tick.  Off, ACLs are stored and returned, nothing more.
 
     ``.port``, ``.address``, ``.servers()`` and ``.shutdown()`` as
     :class:`FakeZKServer`'s; :meth:`call` runs a function on the server's
@@ -153,7 +189,7 @@ class GpuZKServer(object):
 
     def __init__(self, tree, cap_frames, out_cap, max_conns=1024, port=0,
                  tick_ms=1.0, table=None, host='127.0.0.1', raw_cap=1 << 20,
-                 order_passes=0):
+                 order_passes=0, enforce_acl=False):
         if tree.watch is None:
             raise ValueError('GpuZKServer: the tree needs a watch table')
         if table is not None and table.span != 0:
@@ -173,6 +209,10 @@ class GpuZKServer(object):
         if P >= 1 and tree.scratch is None:
             raise ValueError('GpuZKServer: order_passes needs a tree with a '
                              'scratch tail (GpuTree(scratch=...))')
+        self.enforce_acl = bool(enforce_acl)
+        if self.enforce_acl and tree.acl is None:
+            raise ValueError('GpuZKServer: enforce_acl needs a tree with an '
+                             'ACL table (GpuTree(acl_cap=...))')
         self.tree = tree
         self.dev = dev = tree.device
         self.cap_frames = int(cap_frames)
@@ -200,6 +240,11 @@ class GpuZKServer(object):
         self.d_sidx = torch.zeros(S, dtype=I64, device=dev)
         self.segs = SessionSegments(self.d_starts, self.d_sessions,
                                     self.d_wslots)
+        # each row's peer (peer_ipv4), for the ACL check
+        self.h_addrs = _pinned(S, I32, dev)
+        self.np_addrs = self.h_addrs.numpy()
+        self.d_addrs = torch.zeros(S, dtype=I32, device=dev)
+        self.perms = AclIdentity(self.d_addrs) if self.enforce_acl else None
         self._rows_dirty = True
         # -- the cut and the pack ---------------------------------------------
         self.h_raw = _pinned(self.raw_cap, U8, dev)
@@ -230,7 +275,9 @@ class GpuZKServer(object):
         self.d_tx = torch.zeros(self.tx_cap, dtype=U8, device=dev)
         self.h_tx = _pinned(self.tx_cap, U8, dev)
         self.mv_tx = memoryview(self.h_tx.numpy())
-        self.nrep = 4 * S + 1 + (_R_NORD if P else _R_N)
+        # (with enforce_acl one word more, the last: replies answered NO_AUTH)
+        self.nrep = 4 * S + 1 + (_R_NORD if P else _R_N) + \
+            (1 if self.enforce_acl else 0)
         # the ordered tick: the cut's write counts, what the serve deferred;
         # a connection advances by `used`, not by `take`
         self.d_nwr = torch.zeros(S, dtype=I32, device=dev)
@@ -254,7 +301,8 @@ class GpuZKServer(object):
              'bad_batches', 'catchup_events', 'expiry_passes',
              'sessions_expired', 'sessions_closed', 'handshakes',
              'host_reads', 'max_reads_per_tick', 'deferred_frames',
-             'max_writes_per_tick', 'order_max_rank', 'order_scratch_full'),
+             'max_writes_per_tick', 'order_max_rank', 'order_scratch_full',
+             'acl_denied'),
             0)
         self._calls = []
         self._lock = threading.Lock()
@@ -323,7 +371,8 @@ class GpuZKServer(object):
         saw; ``>= order_passes``: it deferred) and ``order_scratch_full``
         (ticks in which a snapshot found no room in the tree's scratch tail:
         the request was answered SYSTEMERROR, a SET_DATA among them after it
-        was applied) — and the last batch's
+        was applied); with ``enforce_acl``: ``acl_denied`` (requests
+        answered NO_AUTH, as of the last tick's report) — and the last batch's
         ``session_stats``, ``watch_stats``, ``resume_stats`` and
         ``close_stats``, each read once."""
         def go():
@@ -436,7 +485,7 @@ class GpuZKServer(object):
     def _accept(self):
         for _ in range(64):
             try:
-                sock, _ = self.lsock.accept()
+                sock, peer = self.lsock.accept()
             except (BlockingIOError, OSError):
                 return
             if not self.free_rows:
@@ -446,6 +495,8 @@ class GpuZKServer(object):
             sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
             c = _Conn(sock, heapq.heappop(self.free_rows))
             self.rows[c.row] = c
+            self.np_addrs[c.row] = peer_ipv4(peer)
+            self._rows_dirty = True
             self.new.append(c)
             self.sel.register(sock, selectors.EVENT_READ, c)
 
@@ -545,6 +596,7 @@ class GpuZKServer(object):
         self.np_sessions[r] = 0
         self.np_wslots[r] = -1
         self.np_sidx[r] = 0
+        self.np_addrs[r] = 0
         self._rows_dirty = True
         heapq.heappush(self.free_rows, r)
 
@@ -639,6 +691,8 @@ class GpuZKServer(object):
             self.d_sessions.copy_(self.h_sessions, non_blocking=True)
             self.d_wslots.copy_(self.h_wslots, non_blocking=True)
             self.d_sidx.copy_(self.h_sidx, non_blocking=True)
+            if self.enforce_acl:
+                self.d_addrs.copy_(self.h_addrs, non_blocking=True)
             self._rows_dirty = False
 
     def _assemble(self, rep_off, out, err, resume, notif, close,
@@ -748,11 +802,11 @@ class GpuZKServer(object):
             out, _, err, _ = gs.serve_sessions_mixed(
                 rx, self.d_starts[S:], self.segs, table=self.table,
                 resume=True, close=True, ordered=True, passes=P,
-                defer=self.defer)
+                defer=self.defer, perms=self.perms)
         else:
             out, _, err, _ = gs.serve_sessions_mixed(
                 rx, self.d_starts[S:], self.segs, table=self.table,
-                resume=True, close=True)
+                resume=True, close=True, perms=self.perms)
         self._assemble(gs.seg.rep_off, out, err,
                        (gs.resume_notif[0], gs.resume_slots[1]),
                        (gs.notif[0], gs.notif_slots[1]),
@@ -766,6 +820,8 @@ class GpuZKServer(object):
         if P:
             words += [self.defer.deferred, self.d_nwr.sum().reshape(1),
                       gs.order_counters()]
+        if self.enforce_acl:
+            words += [gs.acl_enforce_counters()[3:4]]
         rep, total = self._report(words)
         st = self._stats
         st['ticks'] += 1
@@ -780,6 +836,8 @@ class GpuZKServer(object):
                                        int(words[_R_RANK]))
             if words[_R_SCRATCH] > self.tree.scratch.numel():
                 st['order_scratch_full'] += 1
+        if self.enforce_acl:
+            st['acl_denied'] = int(words[-1])       # (the server's own sum)
         st['dup_slot'] += int(words[_R_DUP])
         st['catchup_events'] += int(words[_R_CATCHUP])
         if words[_R_BAD] != 0:
@@ -847,7 +905,8 @@ class GpuZKServer(object):
         rep, total = self._report([
             self.d_none, self.d_none, self.d_over_tx, self.d_none,
             self.d_none, self.d_fstats[0:1], self.d_none, self.d_none] +
-            [self.d_none] * (4 if self.order_passes else 0))
+            [self.d_none] * ((4 if self.order_passes else 0) +
+                             (1 if self.enforce_acl else 0)))
         self._stats['expiry_passes'] += 1
         self._stats['sessions_expired'] += len(due)
         self._deliver(rep, total)
