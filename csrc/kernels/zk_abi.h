@@ -270,8 +270,7 @@ int64_t zk_frame_scan_workspace(int64_t n);
 int zk_frame_scan(const uint8_t*, const int64_t*, int64_t, int64_t,
                   uint8_t*, int64_t, int64_t*, int32_t*, int64_t, int64_t*,
                   int32_t, int32_t, int32_t, hipStream_t);
-int zk_frame_scan_stats(const uint8_t*, int64_t, int32_t, uint32_t*,
-                        hipStream_t);
+int zk_frame_scan_stats(const uint8_t*, int64_t, uint32_t*, hipStream_t);
 int zk_frame_scan_dbg(int64_t* host, int64_t tiles);
 // the tile lists of the scan of buf[0, min(*n_dev, n_cap)) on workspace ws
 // (-1: workspace too small; -2: a stream of one tile at most has none)

@@ -1,6 +1,7 @@
 // K1's (body offset, length) rows from the per-tile frame-start lists that
-// fs_tile / fs_link settled (frame_scan.hip) — the one implementation, used
-// by fs_rows (a wave per tile, the plain scan's third launch) and by the
+// fs_tile / fs_link settled (zk_frame_tile.h, frame_link.hip) — the one
+// implementation, used by fs_rows (frame_scan.hip: a wave per tile, the plain
+// scan's third launch) and by the
 // consumers of a rows-deferred scan (decode_replies_k and tree_serve_k's
 // TILES instances: a workgroup per block of 256 frames), which then need no
 // fs_rows launch and no read-back of the rows it would have written.
@@ -59,7 +60,7 @@ ZK_DEV int32_t lds_be32(const uint8_t* sb, int32_t p) {
 }
 
 // per-tile record: meta = cnt | np << 11 | (js + 1) << 22 | term << 33 |
-// bad << 34 (frame_scan.hip FcWalk)
+// bad << 34 (zk_frame_scan.h FcWalk)
 ZK_DEV int32_t m_cnt(int64_t m) { return (int32_t)(m & 0x7FF); }
 ZK_DEV int32_t m_np(int64_t m) { return (int32_t)((m >> 11) & 0x7FF); }
 ZK_DEV int32_t m_js(int64_t m) { return (int32_t)((m >> 22) & 0x7FF) - 1; }

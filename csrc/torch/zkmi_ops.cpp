@@ -536,11 +536,10 @@ void frame_scan(const Tensor& buf, const c10::optional<Tensor>& n_dev,
          "frame_scan");
 }
 
-std::vector<int64_t> frame_scan_stats(const Tensor& ws, int64_t n_cap,
-                                      int64_t window) {
+std::vector<int64_t> frame_scan_stats(const Tensor& ws, int64_t n_cap) {
   uint32_t o[4] = {0, 0, 0, 0};
-  hip_ok(zk_frame_scan_stats(P<uint8_t>(ws, U8, 1, "ws"), n_cap,
-                             (int32_t)window, o, cur_stream()),
+  hip_ok(zk_frame_scan_stats(P<uint8_t>(ws, U8, 1, "ws"), n_cap, o,
+                             cur_stream()),
          "frame_scan_stats");
   return {o[0], o[1], o[2], o[3]};
 }
@@ -2210,7 +2209,7 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor(d!) result, int window, bool clean=False, int flags=0) "
         "-> ()",
         &frame_scan);
-  m.def("frame_scan_stats(Tensor ws, int n_cap, int window) -> int[]",
+  m.def("frame_scan_stats(Tensor ws, int n_cap) -> int[]",
         &frame_scan_stats);
   m.def("frame_scan_dbg(int tiles) -> Tensor", &frame_scan_dbg);
   m.def("decode_replies(Tensor buf, Tensor frame_off, Tensor frame_len, "

@@ -405,7 +405,7 @@ class FrameScanner:
         self.window = window
         # the stream's usual frame size: >= 128 bytes within a small window
         # lets a wave take a group of tiles (the chain map once, then the
-        # chain walked on; csrc/kernels/frame_scan.hip fs_group_rest).
+        # chain walked on; csrc/kernels/zk_frame_tile.h fs_group_rest).
         # GET reply stream (192-byte frames): 8 tiles a wave 77.4 us, 4
         # tiles 93.0 us (profiles/r4_k1_microbench.md)
         if group is None:
@@ -479,8 +479,7 @@ class FrameScanner:
         if getattr(self, 'last_cap', None) is None:      # no scan yet
             return {'no_spec': 0, 'rewalked': 0, 'rounds': 0, 'looked_up': 0}
         with _on(stream):
-            out = _lib.lib().frame_scan_stats(self.ws, self.last_cap,
-                                              int(self.window))
+            out = _lib.lib().frame_scan_stats(self.ws, self.last_cap)
         return {'no_spec': out[0], 'rewalked': out[1], 'rounds': out[2],
                 'looked_up': out[3]}
 
