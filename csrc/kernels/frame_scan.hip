@@ -211,10 +211,10 @@ int zk_frame_scan(const uint8_t* buf, const int64_t* n_dev, int64_t n_cap,
     return -4;
   int64_t* dbg = fs_dbg_buf(tiles);
   // tiles a wave: groups (the map once, the chain walked on) for streams
-  // of large frames within a small window; tests of the link repair and
-  // long-frame streams take single tiles
+  // of large frames within a small window; long-frame streams take single
+  // tiles (the link repair's test flags apply to a group's first tile)
   int G = ((flags >> 4) & 15) + 1;
-  if ((flags & (FS_LONG | 1 | 0xFFFF00)) || W > 512) G = 1;
+  if ((flags & FS_LONG) || W > 512) G = 1;
   G = G >= 8 ? 8 : G >= 4 ? 4 : G >= 2 ? 2 : 1;
   const TileLaunch tl{buf, n_dev, n_cap, maxp, &v, dbg, flags, W, G,
                       (flags & FS_LONG) != 0};

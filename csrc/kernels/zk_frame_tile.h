@@ -3,6 +3,7 @@
 // launch it).  The design note: zk_frame_scan.h.
 #pragma once
 #include "zk_frame_scan.h"
+#include "zk_run_span.h"
 
 namespace zk {
 
@@ -546,20 +547,26 @@ ZK_DEV void ft_store(uint8_t* sb, const FtTileRegs& r, int lane) {
 // of a 47 us group, tools/microbench/k1_bench.py); streams of varied
 // frames keep the one-address hop (a vector address on every hop cost the
 // 0-200 B GET stream 3 %) and the records gathered 64 to a store.
+// `last` carries the last frame's size across tiles (in: of the frame that
+// ends at c, 0 when unknown; out: of the walk's last frame), so a walked tile
+// of a run begins with run steps; `run` (out): the walk's last two frames were
+// of one size.
 ZK_DEV int64_t ft_walk(const uint8_t* sb, int32_t c, int32_t nrel,
                        int32_t maxp32, int64_t ts, uint16_t* L, int32_t& mo,
-                       int lane) {
+                       int lane, int32_t& last, bool& run) {
   int32_t m = 0, pb = 0;              // records [pb, m) pending in ent
   uint32_t ent = 0;
   int64_t send;
   // (the walk is wave-uniform: the position and the bounds in SGPRs)
   c = __builtin_amdgcn_readfirstlane(c);
   nrel = __builtin_amdgcn_readfirstlane(nrel);
+  last = __builtin_amdgcn_readfirstlane(last);
+  run = false;
   const int32_t lim = min((int32_t)FT_S, nrel);
   if (c >= nrel) {
     send = TERM | (ts + c);
   } else {
-    int32_t len = 0, nx = 0, last = 0;      // last: the last frame's size
+    int32_t len = 0, nx = 0;
     bool ok = true, fin = false;
     while (!fin) {
       len = __builtin_amdgcn_readfirstlane(lds_be32(sb, c));
@@ -573,12 +580,18 @@ ZK_DEV int64_t ft_walk(const uint8_t* sb, int32_t c, int32_t nrel,
         if (q >= pb) L[q] = (uint16_t)ent;
         pb = m;
       }
-      if (nx >= lim) break;
+      if (nx >= lim) {
+        run = 4 + len == last;
+        last = 4 + len;
+        break;
+      }
       c = nx;
       if (4 + len != last) {
         last = 4 + len;
+        run = false;
         continue;
       }
+      run = true;
       // two frames of one size: steps over the run (lane l reads where
       // frame l of it would start); frames 0 .. a-1 lie back to back with
       // that length, and the walk ends after the first reaching the tile's
@@ -753,14 +766,18 @@ ZK_DEV void ft_join(const FtCtx& C, int64_t E, int32_t m, int64_t send,
 
 // Tile t's record (fs_link and the rows read it): the survivor's end code
 // and start count, the entry used (-1: none) and the walk's result.
-ZK_DEV void ft_put_record(const FtCtx& C, int64_t t, int64_t send, int32_t m,
-                          int64_t entry, const FcWalk& wk) {
-  if (C.lane != 0) return;
+// (_lane: written by the calling lane, one tile a lane)
+ZK_DEV void ft_put_record_lane(const FtCtx& C, int64_t t, int64_t send,
+                               int32_t m, int64_t entry, const FcWalk& wk) {
   C.sx[t] = send;
   C.rcount[t] = m;
   C.rec_entry[t] = entry;
   C.rec_exit[t] = wk.exit;
   C.rec_meta[t] = fc_meta(wk);
+}
+ZK_DEV void ft_put_record(const FtCtx& C, int64_t t, int64_t send, int32_t m,
+                          int64_t entry, const FcWalk& wk) {
+  if (C.lane == 0) ft_put_record_lane(C, t, send, m, entry, wk);
 }
 
 // The record of the wave's mapped tile C.t and its ZKMI_FS_DBG row: the
@@ -935,7 +952,9 @@ ZK_DEV int64_t fs_tile_rest(const FtCtx& cx_, bool mapped) {
       }
     } else if (sp >= 0) {
       __builtin_amdgcn_wave_barrier();
-      send = ft_walk(sb, sp, nrel, maxp32, ts, L, m, lane);
+      int32_t last = 0;
+      bool run;
+      send = ft_walk(sb, sp, nrel, maxp32, ts, L, m, lane, last, run);
       if (m == 0) send = -1;
     }
     __builtin_amdgcn_wave_barrier();
@@ -978,33 +997,169 @@ ZK_DEV int64_t ft_cx_of(int64_t send, int32_t m) {
   return (send & TBAD) ? FC_DEAD : FC_LIVE;
 }
 
-// Element q (wave-uniform) of a list held 64 to a register.
-template <int SVN>
-ZK_DEV int32_t ft_sv_at(const uint32_t (&sv)[SVN], int32_t q) {
-  uint32_t v = 0;
+// ---- a run of equal frames, taken by gather --------------------------------
+// The chain enters tile tk at c after two frames of S bytes.  If the run
+// goes on, its frames start at c + j S: lane l reads the length words of
+// frames l, l + 64, ... straight from global memory (FT_NGI loads, all
+// issued before the first wait; a word not wholly inside the stream is not
+// loaded), and the leading frames whose word repeats the length, that end
+// inside the stream, are by induction what the hop-by-hop walk finds.  The
+// tiles that prefix covers whole get the records the staged walk writes,
+// computed (zk_run_span.h): none of their 4 KiB is staged, and a 192-byte
+// reply costs one 64-byte sector, not three.  Returns the tiles covered (0:
+// the caller walks tile tk: a false trigger costs this one round trip); `send`
+// the chain's exit from the last of them; `full`: every word asked for was
+// accepted and the group has frames left (gather again).
+constexpr int FT_NGI = 4;
+static_assert(RUN_TILE == FT_S, "zk_run_span.h: the tile");
+struct FtGather {
+  uint32_t w[FT_NGI];          // this lane's words: frames lane + 64 i
+  int32_t crel, S, room, want, nrel;
+  int64_t g_0;
+};
+// (issued apart from ft_gather_take: the caller puts work under the loads)
+ZK_DEV FtGather ft_gather_issue(const FtCtx& C, int64_t c, int32_t S,
+                                int64_t tk, int64_t gend) {
+  FtGather g;
+  const int64_t tsk = tk * FT_S;
+  // (wave-uniform: the position and the size in SGPRs)
+  g.crel = __builtin_amdgcn_readfirstlane((int32_t)(c - tsk));
+  g.S = __builtin_amdgcn_readfirstlane(S);
+  g.g_0 = C.dbg ? wall_clock64() : 0;
+  g.room = (int32_t)(gend - tk);
+  g.nrel = (int32_t)min(C.n - tsk, (int64_t)1 << 30);
+  g.want = run_want(g.crel, g.S, g.room * FT_S, 64 * FT_NGI);
+  const uint8_t* tb = C.buf + tsk;
 #pragma unroll
-  for (int i = 0; i < SVN; ++i)
-    if (i == (q >> 6)) v = sv[i];
-  return __builtin_amdgcn_readlane((int)v, q & 63);
+  for (int i = 0; i < FT_NGI; ++i) {
+    const int32_t j = C.lane + 64 * i;
+    const int32_t prel = g.crel + j * g.S;
+    g.w[i] = 0;
+    if (j < g.want && run_word_in(prel, g.nrel))
+      __builtin_memcpy(&g.w[i], tb + prel, 4);
+  }
+  return g;
+}
+ZK_DEV int32_t ft_gather_take(const FtCtx& C, const FtGather& g, int64_t tk,
+                              int64_t& send, bool& full) {
+  const int lane = C.lane;
+  const int64_t n = C.n, tsk = tk * FT_S;
+  const int32_t crel = g.crel, S = g.S, want = g.want, room = g.room;
+  const uint32_t(&w)[FT_NGI] = g.w;
+  const int64_t g_0 = g.g_0;
+  const int64_t g_1 =
+      C.dbg ? (__builtin_amdgcn_s_waitcnt(0), wall_clock64()) : 0;
+  int32_t a = 0;
+  bool open = true;
+#pragma unroll
+  for (int i = 0; i < FT_NGI; ++i) {
+    const int32_t j = lane + 64 * i;
+    const int32_t prel = crel + j * S;
+    const bool acc = j < want && run_word_in(prel, g.nrel) &&
+                     run_accept((int32_t)bswap32(w[i]), S, prel, g.nrel,
+                                C.maxp32);
+    const uint64_t no = ~__ballot(acc);
+    const int32_t ai = no ? (int32_t)__builtin_ctzll(no) : 64;
+    a += open ? ai : 0;
+    open = open && ai == 64;
+  }
+  full = a == 64 * FT_NGI;
+  const int32_t cov = min(run_tiles_covered(crel, S, a), room);
+  if (cov == 0) return 0;
+  const int64_t g_2 = C.dbg ? wall_clock64() : 0;
+  // the tiles' records, one lane a tile
+  int32_t rfirst = 0;
+  if (lane < cov) {
+    const RunTile r = run_tile(crel, S, a, lane);
+    rfirst = r.first;
+    const int64_t tq = tk + lane;
+    const int64_t entry = tsk + r.entry, exit = tsk + r.exit;
+    FcWalk wk{entry, r.count, 0, r.count > 0 ? 0 : -1, false, false};
+    fc_join_end(wk, exit, n);
+    ft_put_record_lane(C, tq, exit, r.count, entry, wk);
+    lb_store(&C.lbw[2 * (tq - 1)],
+             (uint64_t)1 << 63 | (uint64_t)(entry - tq * FT_S + 1));
+    C.cx[5 * tq] = ft_cx_of(exit, r.count);
+#pragma unroll
+    for (int s = 1; s < 5; ++s) C.cx[5 * tq + s] = FC_DEAD;
+    if (C.dbg) {
+      // (dbg: a gathered tile's row — the gather's issue, its arrival, the
+      // prefix known, the records)
+      int64_t* const dk = C.dbg + 8 * tq;
+      dk[0] = g_0;
+      dk[1] = g_1;
+      dk[2] = g_2;
+      dk[3] = wall_clock64();
+      dk[5] = (int64_t)r.count;
+    }
+  }
+  // the frame starts: one lane a frame, into its tile's list (the tile's
+  // first frame from the lane that wrote its record)
+#pragma unroll
+  for (int i = 0; i < FT_NGI; ++i) {
+    const int32_t j = lane + 64 * i;
+    const int32_t prel = crel + j * S;
+    const int32_t q = prel >> 12;
+    // (the shuffle with every lane active: it reads lane q's register)
+    const int32_t first = __shfl(rfirst, q & 63, 64);
+    if (j < a && q < cov) {
+      C.list[(tk + q) * FT_LMAX + (j - first)] = (uint16_t)(prel & (FT_S - 1));
+    }
+  }
+  send = tsk + run_tile(crel, S, a, cov - 1).exit;
+  return cov;
 }
 
 // The group's other tiles: the chain leaving tile t0 (end code send0; alive:
-// the tile has one) walked on through them, each tile's records and its one
-// candidate entry written as it goes; then the group's last exit published
-// as the next group's candidate.  `nxt` holds tile t0 + 1, loaded by the
-// caller (its load overlaps the caller's work).
+// the tile has one; last / run: its last frame's size and whether the frame
+// before had it too) followed through them — a run of equal frames by
+// gather, anything else walked through the staged tile — each tile's
+// records and its one candidate entry written as it goes; then the group's
+// last exit published as the next group's candidate.  `nxt` holds tile
+// t0 + 1, loaded by the caller (its load overlaps the caller's work); a
+// walked tile loads the one after it under its walk, a gathered one loads
+// nothing.
 template <int W, int G>
 ZK_DEV void ft_group_tail(const FtCtx& C, int64_t send0, bool alive,
-                          FtTileRegs& nxt) {
+                          FtTileRegs& nxt, int32_t last, bool run) {
   const int lane = C.lane;
   uint8_t* sb = C.sb;
   const int64_t n = C.n, t0 = C.t;
   const int32_t maxp32 = C.maxp32;
   const int64_t ntiles = (n + FT_S - 1) / FT_S;
-  // ---- the group's other tiles: the survivor's chain walked on -----------
+  const int64_t gend = min(t0 + G, ntiles);
   int64_t send = send0;
   int32_t kdone = 1;
-  for (int k = 1; k < G; ++k) {
+  int k = 1;
+  // ---- a run leaving tile t0: taken by gather, round after round ---------
+  // (tile t0 + 1, which nxt holds, goes to LDS under the first gather: the
+  // walk's, should the run break in it)
+  // (the 256-byte window's instances only: with the 512-byte window's
+  // larger entry table the gather's registers cost the third wave a SIMD.
+  // The 256-byte ones stand at 163 VGPRs with it, 5 below the 168 that 3
+  // waves a SIMD allow: check tools/kernel_resources.py after any change to
+  // the grouped path, profiles/run_gather_resources.md)
+  if (W <= 256 && run && last >= 16 && last <= FT_S && t0 + 1 < ntiles &&
+      alive && !(send & TERM)) {
+    bool full = true, first = true;
+    while (full && k < G && t0 + k < ntiles && send >= (t0 + k) * FT_S &&
+           send < (t0 + k + 1) * FT_S) {
+      const FtGather g = ft_gather_issue(C, send, last, t0 + k, gend);
+      if (first) ft_store(sb, nxt, lane);
+      first = false;
+      const int32_t cov = ft_gather_take(C, g, t0 + k, send, full);
+      if (cov == 0) break;
+      k += cov;
+    }
+    kdone = k;
+    // (the tile the run ends in: its bytes on demand.  No tile rides in
+    // registers while a gather is taken, so a run that ends in tile t0 + 1
+    // loads that tile again, from L2)
+    if (k < G && t0 + k < ntiles)
+      ft_load(C.buf, n, (t0 + k) * FT_S, lane, nxt);
+  }
+  // ---- the group's other tiles: the survivor's chain walked on -----------
+  for (; k < G; ++k) {
     const int64_t tk = t0 + k;
     if (tk >= ntiles) break;
     const int64_t tsk = tk * FT_S;
@@ -1022,7 +1177,7 @@ ZK_DEV void ft_group_tail(const FtCtx& C, int64_t send0, bool alive,
     int32_t m;
     const int32_t nrelk = (int32_t)min(n - tsk, (int64_t)1 << 30);
     send = ft_walk(sb, (int32_t)(c - tsk), nrelk, maxp32, tsk,
-                   C.list + tk * FT_LMAX, m, lane);
+                   C.list + tk * FT_LMAX, m, lane, last, run);
     const int64_t k_2 = dk ? wall_clock64() : 0;
     FcWalk wk{c, m, 0, m > 0 ? 0 : -1, false, false};
     fc_join_end(wk, send, n);
@@ -1107,24 +1262,36 @@ ZK_DEV void fs_group_rest(const FtCtx& cx_) {
     } else {
       // (a side branch or a short frame on it: walked)
       __builtin_amdgcn_wave_barrier();
-      send0 = ft_walk(sb, sp, nrel, maxp32, ts, L0, m0, lane);
+      int32_t last = 0;
+      bool run;
+      send0 = ft_walk(sb, sp, nrel, maxp32, ts, L0, m0, lane, last, run);
       for (int32_t k = lane; k < m0; k += 64) C.slot[k] = L0[k];
       ws = 0;                  // (the slots hold the walk's starts)
     }
   }
-  // the survivor's starts stay in registers (R becomes the survivor bits
-  // if tile t0 has to come back)
-  constexpr int SVN = (FT_SLOTS + 63) / 64;
+  // the survivor's starts move to the node words' LDS, which nothing reads
+  // after the map (R becomes the survivor bits if tile t0 has to come back;
+  // in registers they were 6 VGPRs carried across the whole tail)
+  static_assert(FT_SLOTS * 2 <= FT_NMAX * 4, "the starts fit the node words");
   __builtin_amdgcn_wave_barrier();
-  uint32_t sv[SVN];
-#pragma unroll
-  for (int i = 0; i < SVN; ++i)
-    sv[i] = lane + 64 * i < m0 ? C.slot[lane + 64 * i] : 0u;
+  uint16_t* const sv = (uint16_t*)C.pk;
+  for (int32_t k = lane; k < m0; k += 64) sv[k] = C.slot[k];
+  __builtin_amdgcn_wave_barrier();
+  // the run state the tail starts from: the chain's last frame's size, and
+  // whether the frame before had it too
+  int32_t last0 = 0;
+  bool run0 = false;
+  if (m0 >= 1 && send0 >= 0 && !(send0 & TERM)) {
+    const int32_t a = __builtin_amdgcn_readfirstlane(sv[m0 - 1]);
+    const int32_t b = __builtin_amdgcn_readfirstlane(sv[m0 >= 2 ? m0 - 2 : 0]);
+    last0 = (int32_t)(send0 - ts) - a;
+    run0 = m0 >= 2 && a - b == last0;
+  }
   const int64_t t_1 = C.dbg ? wall_clock64() : 0;
 
   FtTileRegs nxt;
   if (G > 1 && t0 + 1 < ntiles) ft_load(C.buf, n, ts + FT_S, lane, nxt);
-  ft_group_tail<W, G>(C, send0, sp >= 0, nxt);
+  ft_group_tail<W, G>(C, send0, sp >= 0, nxt, last0, run0);
 
   // ---- the first tile's entry: the group before's exit -------------------
   int64_t E = 0;
@@ -1138,17 +1305,15 @@ ZK_DEV void fs_group_rest(const FtCtx& cx_) {
     ft_load(C.buf, n, ts, lane, r);
     ft_store(sb, r, lane);
     // survivor bits from the survivor's starts
-    // (start i is in register i / 64 of lane i % 64: this lane's own)
-    ft_survivor_bits(C.sbits, m0, lane, [&](int i) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < SVN; ++k)
-        if (k == (i >> 6)) v = sv[k];
-      return v;
-    });
+    ft_survivor_bits(C.sbits, m0, lane,
+                     [&](int i) { return (uint32_t)sv[i]; });
     staged = true;
   };
-  if (t0 > 0) {
+  if (t0 > 0 && C.nospec) {
+    // (tests: no group takes a speculated entry, as fs_tile_rest)
+    none = true;
+    if (lane < 5) C.cx[5 * t0 + lane] = FC_DEAD;
+  } else if (t0 > 0) {
     const uint64_t xw = ft_wait_prev(C.lbw, t0);
     // lane s: candidate s, looked up in the window table (the lane owning
     // position e holds its root in register e / 64)
@@ -1195,6 +1360,12 @@ ZK_DEV void fs_group_rest(const FtCtx& cx_) {
     }
     if (lane < 5) C.cx[5 * t0 + lane] = xe;
     E = ft_pick(ts, has, e, xe, we, open, wE, known);
+    // (tests: every misspec-th group takes a garbage entry one byte past the
+    // chosen one, as fs_tile_rest's tiles do)
+    if (C.misspec > 0 && (t0 / G) % C.misspec == 1 && E >= 0 && E + 1 < n) {
+      ++E;
+      known = false;
+    }
     none = E < 0;
   } else {
     wE = rw[0];                 // lane 0's position 0
@@ -1212,7 +1383,8 @@ ZK_DEV void fs_group_rest(const FtCtx& cx_) {
     done = true;
   } else if (!none && known && ws != 0 && (wE >> 16) == (ws >> 16) &&
              (int32_t)rk_cnt(wE) <= m0 && rk_cnt(wE) > 0 &&
-             ft_sv_at<SVN>(sv, m0 - (int32_t)rk_cnt(wE)) == erel) {
+             __builtin_amdgcn_readfirstlane(
+                 (int32_t)sv[m0 - (int32_t)rk_cnt(wE)]) == erel) {
     // the entry is on the survivor's chain: the rest is its list
     wk.js = m0 - (int32_t)rk_cnt(wE);
     wk.cnt = (int32_t)rk_cnt(wE);
@@ -1394,7 +1566,7 @@ __global__ __launch_bounds__(256) void fs_tile(
       const int64_t s0 = fs_tile_rest<W, LONG, 1>(C, false);
       FtTileRegs nxt;
       if (t + 1 < (n + FT_S - 1) / FT_S) ft_load(buf, n, ts + FT_S, lane, nxt);
-      ft_group_tail<W, G>(C, s0, s0 >= 0, nxt);
+      ft_group_tail<W, G>(C, s0, s0 >= 0, nxt, 0, false);
     }
   } else {
     if (N <= 128) fs_tile_rest<W, LONG, 2>(C, true);
