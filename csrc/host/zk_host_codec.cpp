@@ -28,7 +28,7 @@ PyObject* g_decode_err = nullptr;   // zkmi.errors.ZKDecodeError
 struct Names {
   PyObject *xid, *zxid, *err, *opcode, *path, *data, *stat, *children, *acl,
       *type, *state, *watch, *version, *flags, *perms, *id, *scheme, *relZxid,
-      *events, *dataChanged, *createdOrDestroyed, *childrenChanged;
+      *events, *dataChanged, *createdOrDestroyed, *childrenChanged, *auth;
 } N;
 
 struct Code { int32_t code; const char* name; PyObject* obj; };
@@ -472,6 +472,13 @@ bool encode_request_into(PyObject* d, std::string* out, bool framed) {
            write_vec(w, get(ev, N.childrenChanged));
       break;
     }
+    case 100: {                                      // AUTH
+      // AuthPacket: type (unused, 0), scheme, auth
+      PyObject* sc = get(d, N.scheme);
+      w.i32((int32_t)as_long(get(d, N.type), 0));
+      ok = sc && w.ustr(sc) && w.bytes(get(d, N.auth));
+      break;
+    }
     case 11: case -11:                               // PING, CLOSE_SESSION
       break;
     default:
@@ -590,7 +597,7 @@ PyMODINIT_FUNC PyInit__zkhost(void) {
   I(xid); I(zxid); I(err); I(opcode); I(path); I(data); I(stat);
   I(children); I(acl); I(type); I(state); I(watch); I(version); I(flags);
   I(perms); I(id); I(scheme); I(relZxid); I(events); I(dataChanged);
-  I(createdOrDestroyed); I(childrenChanged);
+  I(createdOrDestroyed); I(childrenChanged); I(auth);
 #undef I
   intern(g_ops); intern(g_errs); intern(g_ntypes); intern(g_states);
   intern(g_perms); intern(g_flags);

@@ -213,6 +213,18 @@ struct ZkAclTable {
   int64_t* ctr;
 };
 
+// The identities the connections of a session batch hold after AUTH
+// (tree_auth.hip; the rule and the record layout: zk_auth.h).  ZooKeeper keeps
+// authentication per connection, so the row is the segment index.
+struct ZkAuthTable {
+  // [S * zk_auth_row_bytes()] per row 4 records of 160 bytes: the id's length
+  // (native int32), then up to 148 id bytes
+  uint8_t* recs;
+  int32_t* cnt;       // [S] records claimed in the row (readers clamp to 4)
+  int64_t* stats;     // [8] ok, failed, full, known, answered OK / AUTH_FAILED
+  int64_t S;
+};
+
 // K1's per-tile frame-start lists, as a consumer of a rows-deferred scan
 // (zk_frame_scan flags bit 24) reads them: zk_frame_rows.h turns a
 // workgroup's 256 frames into (body offset, length) rows from these, and
@@ -581,6 +593,26 @@ int zk_aclperm_check(const ZkTree*, const ZkAclTable*, uint8_t*, int64_t,
                      hipStream_t);
 int zk_aclperm_fix(const int32_t*, const int32_t*, const int32_t*,
                    const int64_t*, int64_t, int32_t*, int64_t*, hipStream_t);
+// AUTH with digest identities around a session batch (tree_auth.hip; the rule:
+// zk_auth.h).  zk_auth_frames, after zk_sess_assign and before the ACL check:
+// (rx, its length, frames off / len, count, ncap, the whole batch's segment
+// table, the identity table of at least as many rows) -> res[ncap] (0 not an
+// AUTH frame or a refused segment, 1 stored, 2 AUTH_FAILED), the new
+// identities in the table, its stats[0..3] += (ok, failed, full, known).
+// zk_aclperm_check_auth: zk_aclperm_check where a `digest` entry grants to a
+// row that holds its id.  zk_auth_fix, where zk_aclperm_fix runs: (res, the
+// split's cls / sub, the whole batch's count, ncap) -> the serve's r_err of an
+// AUTH frame OK or AUTH_FAILED, stats[4], stats[5] += the replies so answered.
+int64_t zk_auth_row_bytes(void);
+int zk_auth_frames(const uint8_t*, int64_t, const int64_t*, const int32_t*,
+                   const int64_t*, int64_t, const ZkSegs*, const ZkAuthTable*,
+                   int32_t*, hipStream_t);
+int zk_aclperm_check_auth(const ZkTree*, const ZkAclTable*, uint8_t*, int64_t,
+                          const int64_t*, const int32_t*, const int64_t*,
+                          int64_t, const ZkSegs*, const int32_t*,
+                          const ZkAuthTable*, int32_t*, int64_t*, hipStream_t);
+int zk_auth_fix(const int32_t*, const int32_t*, const int32_t*, const int64_t*,
+                int64_t, int32_t*, int64_t*, hipStream_t);
 // The front end's I/O staging (front.hip; the rules: zk_front.h).
 // zk_front_chunk: bytes of the cut's staged window.  zk_front_cut: (raw, n,
 // raw_starts[S + 1], S, quota, max_packet) -> take[S], nfr[S], flag[S],

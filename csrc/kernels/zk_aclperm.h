@@ -105,7 +105,9 @@ ZK_HD bool aclperm_is(const uint8_t* __restrict__ p, int64_t n,
 
 // Does the vector [vec, vec + len) grant `perm` to a peer at addr?  world
 // matches with the id "anyone" only, ip as above; every other scheme (digest,
-// auth, sasl, ...) matches nobody: this server has no AUTH.  A count or a
+// auth, sasl, ...) matches nobody: the peer here has no identity but its
+// address (zk_auth.h aclperm_permits_auth: one that holds digest identities).
+// A count or a
 // length that leaves the vector ends the walk: denied.  (A negative string
 // length is Jute's null string: empty, as skip_acl takes it.)
 ZK_HD bool aclperm_permits(const uint8_t* __restrict__ vec, int64_t len,

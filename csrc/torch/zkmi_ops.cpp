@@ -2022,6 +2022,92 @@ void aclperm_fix(const Tensor& deny, const Tensor& cls, const Tensor& sub,
          "aclperm_fix");
 }
 
+// AUTH with digest identities around a session batch (tree_auth.hip).  The
+// identity table: [recs uint8 [S * row bytes], cnt int32 [S], stats int64 [8]].
+ZkAuthTable auth_table(const std::vector<Tensor>& v, const Tensor* r) {
+  need(v, 3, "auth table");
+  ZkAuthTable a;
+  a.S = v[1].numel();
+  TORCH_CHECK(a.S >= 1 && a.S < (1ll << 24), "zkmi: an auth table has 1 .. "
+              "2^24 rows");
+  a.recs = P<uint8_t>(v[0], U8, a.S * zk_auth_row_bytes(), "auth.recs", r);
+  a.cnt = P<int32_t>(v[1], I32, a.S, "auth.cnt", r);
+  a.stats = P<int64_t>(v[2], I64, 8, "auth.stats", r);
+  return a;
+}
+
+int64_t auth_row_bytes() { return zk_auth_row_bytes(); }
+
+// The batch's AUTH frames (the whole batch's frames and segment table) ->
+// res [ncap], the identities stored in auth's rows, its counters.
+void auth_frames(const Tensor& rx, const Tensor& foff, const Tensor& flen,
+                 const Tensor& n_dev, int64_t ncap,
+                 const std::vector<Tensor>& sg,
+                 const std::vector<Tensor>& auth, const Tensor& res) {
+  const Tensor* d = &rx;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: auth_frames ncap");
+  const ZkSegs m = segs(sg, ncap, d);
+  const ZkAuthTable au = auth_table(auth, d);
+  TORCH_CHECK(au.S >= m.S, "zkmi: the auth table has ", au.S,
+              " rows, sessions ", m.S);
+  hip_ok(zk_auth_frames(P<uint8_t>(rx, U8, 1, "rx"), rx.numel(),
+                        P<int64_t>(foff, I64, ncap, "frame_off", d),
+                        P<int32_t>(flen, I32, ncap, "frame_len", d),
+                        P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m, &au,
+                        P<int32_t>(res, I32, ncap, "res", d), cur_stream()),
+         "auth_frames");
+}
+
+// aclperm_check for peers with identities: a digest entry grants to a row of
+// auth that holds its id.
+void aclperm_check_auth(const std::vector<Tensor>& t,
+                        const std::vector<Tensor>& acl, const Tensor& rx,
+                        const Tensor& foff, const Tensor& flen,
+                        const Tensor& n_dev, int64_t ncap,
+                        const std::vector<Tensor>& sg, const Tensor& addrs,
+                        const std::vector<Tensor>& auth, const Tensor& deny,
+                        const Tensor& stats) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a = acl_table(acl, d);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1,
+              "zkmi: aclperm_check_auth ncap");
+  const ZkSegs m = segs(sg, ncap, d);
+  const ZkAuthTable au = auth_table(auth, d);
+  TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+              " elements, needs ", s.store.cap);
+  TORCH_CHECK(addrs.numel() == m.S, "zkmi: addrs has ", addrs.numel(),
+              " entries, sessions ", m.S);
+  TORCH_CHECK(au.S >= m.S, "zkmi: the auth table has ", au.S,
+              " rows, sessions ", m.S);
+  hip_ok(zk_aclperm_check_auth(
+             &s, &a, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m,
+             P<int32_t>(addrs, I32, m.S, "addrs", d), &au,
+             P<int32_t>(deny, I32, ncap, "deny", d),
+             P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "aclperm_check_auth");
+}
+
+// The fix-up between the serve and its reply encode: an AUTH frame of the
+// serve's class whose reply the serve left BAD_ARGUMENTS -> OK (res 1) or
+// AUTH_FAILED (res 2) in r_err, counted in stats[4] / stats[5].
+void auth_fix(const Tensor& res, const Tensor& cls, const Tensor& sub,
+              const Tensor& n_dev, int64_t ncap, const Tensor& r_err,
+              const Tensor& stats) {
+  const Tensor* d = &res;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: auth_fix ncap");
+  hip_ok(zk_auth_fix(P<int32_t>(res, I32, ncap, "res"),
+                     P<int32_t>(cls, I32, ncap, "cls", d),
+                     P<int32_t>(sub, I32, ncap, "sub", d),
+                     P<int64_t>(n_dev, I64, 1, "count", d), ncap,
+                     P<int32_t>(r_err, I32, ncap, "r_err", d),
+                     P<int64_t>(stats, I64, 8, "stats", d), cur_stream()),
+         "auth_fix");
+}
+
 // Passes 2-7.  sids given: the direct form, K = its length (wslots, when
 // given, as long); else the list close_frames left in ws.  S: the sessions
 // the workspace was sized for (K <= S; removed has room for S).
@@ -2449,6 +2535,16 @@ TORCH_LIBRARY(zkmi, m) {
         "-> ()", &aclperm_check);
   m.def("aclperm_fix(Tensor deny, Tensor cls, Tensor sub, Tensor count, "
         "int ncap, Tensor(a!) r_err, Tensor(b!) stats) -> ()", &aclperm_fix);
+  m.def("auth_row_bytes() -> int", &auth_row_bytes);
+  m.def("auth_frames(Tensor rx, Tensor frame_off, Tensor frame_len, "
+        "Tensor count, int ncap, Tensor[] segs, Tensor(a!)[] auth, "
+        "Tensor(b!) res) -> ()", &auth_frames);
+  m.def("aclperm_check_auth(Tensor[] tree, Tensor[] acl, Tensor(a!) rx, "
+        "Tensor frame_off, Tensor frame_len, Tensor count, int ncap, "
+        "Tensor[] segs, Tensor addrs, Tensor[] auth, Tensor(b!) deny, "
+        "Tensor(c!) stats) -> ()", &aclperm_check_auth);
+  m.def("auth_fix(Tensor res, Tensor cls, Tensor sub, Tensor count, "
+        "int ncap, Tensor(a!) r_err, Tensor(b!) stats) -> ()", &auth_fix);
   m.def("front_chunk() -> int", &front_chunk);
   m.def("front_cut(Tensor raw, int n, Tensor raw_starts, int quota, "
         "int max_packet, Tensor(a!) take, Tensor(b!) nfr, Tensor(c!) flag, "

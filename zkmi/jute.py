@@ -411,6 +411,11 @@ def encode_request(pkt):
         w.write_string_vector(ev.get('dataChanged', []))
         w.write_string_vector(ev.get('createdOrDestroyed', []))
         w.write_string_vector(ev.get('childrenChanged', []))
+    elif op == 'AUTH':
+        # AuthPacket: type (unused, 0), scheme, auth
+        w.write_int(pkt.get('type', 0))
+        w.write_ustring(pkt['scheme'])
+        w.write_buffer(pkt.get('auth', b''))
     elif op in ('PING', 'CLOSE_SESSION'):
         pass
     else:
@@ -418,8 +423,13 @@ def encode_request(pkt):
     return w.getvalue()
 
 
-def decode_request(body):
-    """Server-mode request decode (``zk-buffer.js:58-95``, ``:138-253``)."""
+def decode_request(body, auth=False):
+    """Server-mode request decode (``zk-buffer.js:58-95``, ``:138-253``).
+    ``auth``: an AUTH request is decoded too (type, scheme, auth).  Off, it
+    is an unsupported opcode, as it is for the GPU server's request parse
+    (csrc/kernels/zk_wire.h parse_request), whose oracle this function is:
+    there AUTH frames are served by a pass of their own
+    (csrc/kernels/zk_auth.h auth_frame)."""
     r = JuteReader(body)
     pkt = {}
     pkt['xid'] = r.read_int()
@@ -450,6 +460,10 @@ def decode_request(body):
             'createdOrDestroyed': r.read_string_vector(),
             'childrenChanged': r.read_string_vector(),
         }
+    elif op == 'AUTH' and auth:
+        pkt['type'] = r.read_int()
+        pkt['scheme'] = r.read_ustring()
+        pkt['auth'] = r.read_buffer()
     elif op in ('PING', 'CLOSE_SESSION'):
         pass
     else:

@@ -145,6 +145,8 @@ class Client(FSM):
             else list(o.get('listeners') or ())
         self.session = None
         self.old_session = None
+        # credentials add_auth had accepted: sent again on every connect
+        self._auths = []
         self.conns = {}
         self.hdls = {}
         self.loop.run(self._init_on_loop)
@@ -154,6 +156,7 @@ class Client(FSM):
         for evt, fn in self._early:
             self.on(evt, fn)
         self._early = None
+        self.on('connect', self._resend_auth)
         self.resolver = StaticResolver(self.servers, consts.DEFAULT_PORT)
         self.cset = ConnectionSet(self.resolver, self._makeConnection,
                                  self.loop, self.log, self.config)
@@ -528,6 +531,48 @@ class Client(FSM):
         _check_func(cb)
         self._request({'opcode': 'SYNC', 'path': path}, cb,
                       lambda pkt: cb(None))
+
+    def add_auth(self, scheme, auth, cb=None):
+        """Add credentials to the connection (ZooKeeper's ``addAuthInfo``):
+        ``scheme`` (``'digest'``) and ``auth`` (bytes or str,
+        ``b'user:password'`` for digest).  An ordinary AUTH request with an
+        ordinary xid — a server echoes whatever xid an AUTH frame carries.
+        ``cb(None)`` on success, ``cb(ZKError)`` with code ``AUTH_FAILED``
+        when the server refuses them.
+
+        A server keeps authentication per connection, so the client
+        remembers credentials that succeeded and sends them again on every
+        new connection, from its own ``'connect'`` handling.  A request
+        issued from a ``'connect'`` listener that was registered earlier
+        (the ``listeners`` option) may overtake the re-sent AUTH and be
+        answered before the connection holds the identity."""
+        _check_str(scheme, 'scheme')
+        if isinstance(auth, str):
+            auth = auth.encode('utf-8')
+        auth = bytes(auth)
+        if cb is not None:
+            _check_func(cb)
+
+        def done(err):
+            if err is None and (scheme, auth) not in self._auths:
+                self._auths.append((scheme, auth))
+            if cb is not None:
+                cb(err)
+        self._request({'opcode': 'AUTH', 'type': 0, 'scheme': scheme,
+                       'auth': auth}, done, lambda pkt: done(None))
+
+    addAuth = add_auth
+
+    def _resend_auth(self):
+        """On ``'connect'``: the remembered credentials for the new
+        connection (it starts without any)."""
+        for scheme, auth in list(self._auths):
+            def failed(err, scheme=scheme):
+                if err is not None:
+                    self.log.warn(err, 'could not add %s credentials again '
+                                  'after a reconnect', scheme)
+            self._request({'opcode': 'AUTH', 'type': 0, 'scheme': scheme,
+                           'auth': auth}, failed, lambda pkt: None)
 
     # -- bulk (GPU-coded, pipelined) API (models/bulk.py) ---------------------
 

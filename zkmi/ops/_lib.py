@@ -520,6 +520,56 @@ def aclperm_fix(deny, cls, sub, count, ncap, r_err, stats):
     lib().aclperm_fix(deny, cls, sub, count, int(ncap), r_err, stats)
 
 
+# AUTH with digest identities around a session batch
+# (csrc/kernels/tree_auth.hip; the rule and the record layout: zk_auth.h).
+# What GpuServer.auth_stats reports, in order (stats[0..5])
+AUTH_STATS = ('ok', 'failed', 'full', 'known', 'answered_ok',
+              'answered_failed')
+AUTH_K, AUTH_REC, AUTH_ID_MAX, AUTH_MAX = 4, 160, 148, 119
+AUTH_FAILED = -115
+
+
+def auth_row_bytes():
+    """Bytes of one row of an identity table's records
+    (:data:`AUTH_K` records of :data:`AUTH_REC` bytes)."""
+    return lib().auth_row_bytes()
+
+
+def auth_frames(rx, frame_off, frame_len, count, ncap, segs, auth, res):
+    """After :func:`sess_assign` and before the ACL check, on the current
+    stream: every AUTH frame (opcode 100) of the whole batch's frame table
+    whose segment is served (``segs``: the whole batch's table) is parsed
+    and, for the scheme ``digest`` and credentials of at most
+    :data:`AUTH_MAX` bytes, its identity ``user:base64(SHA1(credentials))``
+    stored in row ``f_seg[i]`` of ``auth`` (``[recs, cnt, stats]``) unless
+    the row holds it.  ``res`` (int32 [ncap]) is written for the batch's
+    frames: 0 not an AUTH frame or a refused segment, 1 stored or known,
+    2 AUTH_FAILED (malformed, another scheme, too long, the row is full).
+    ``auth[2]`` accumulates :data:`AUTH_STATS` [0..3].  One launch, no host
+    read."""
+    lib().auth_frames(rx, frame_off, frame_len, count, int(ncap), list(segs),
+                      list(auth), res)
+
+
+def aclperm_check_auth(tree, acl, rx, frame_off, frame_len, count, ncap, segs,
+                       addrs, auth, deny, stats):
+    """:func:`aclperm_check` for peers that hold identities: a ``digest``
+    entry that carries the bit grants when its id is one of row
+    ``f_seg[i]``'s identities in ``auth``.  One launch, no host read."""
+    lib().aclperm_check_auth(tree, list(acl), rx, frame_off, frame_len, count,
+                             int(ncap), list(segs), addrs, list(auth), deny,
+                             stats)
+
+
+def auth_fix(res, cls, sub, count, ncap, r_err, stats):
+    """Where :func:`aclperm_fix` runs: an AUTH frame (``res`` of
+    :func:`auth_frames`; ``cls`` / ``sub`` / ``count``:
+    :func:`tree_mix_split`'s over the whole batch) whose reply the serve left
+    BAD_ARGUMENTS is answered OK (1) or AUTH_FAILED (2) in ``r_err`` and
+    counted in ``stats[4]`` / ``stats[5]``.  One launch, no host read."""
+    lib().auth_fix(res, cls, sub, count, int(ncap), r_err, stats)
+
+
 # the front end's TX streams, in the order a connection's pieces are sent
 # (csrc/kernels/zk_front.h FS_*), and its assembly counters (FTS_*)
 FS_REPLY, FS_RESUME, FS_NOTIF, FS_CLOSE = range(4)

@@ -48,13 +48,63 @@ class AclIdentity(object):
     zk_aclperm.h): ``addrs``, a device int32 [S] tensor, segment s's peer
     IPv4 address as a host-order 32-bit word (10.1.2.9 is ``0x0A010209``; a
     value past 2^31 as its two's complement) or 0 for a peer without one,
-    which no ``ip`` entry matches."""
+    which no ``ip`` entry matches.  ``auth`` (an :class:`AuthTable` of at
+    least S rows, or None): the batch's AUTH frames are served and a
+    ``digest`` entry matches a connection that holds its id."""
 
-    def __init__(self, addrs):
+    def __init__(self, addrs, auth=None):
         if addrs.dtype != I32 or addrs.dim() != 1 or addrs.numel() < 1:
             raise ValueError('AclIdentity: addrs is an int32 [S] tensor')
         self.addrs = addrs
         self.S = int(addrs.numel())
+        if auth is not None and (not isinstance(auth, AuthTable) or
+                                 auth.S < self.S):
+            raise ValueError('AclIdentity: auth is an AuthTable of at least '
+                             'S rows')
+        self.auth = auth
+
+
+class AuthTable(object):
+    """The ``digest`` identities the connections of a session batch hold
+    after AUTH (csrc/kernels/tree_auth.hip; the rule and the record layout:
+    zk_auth.h).  ZooKeeper keeps authentication per connection, not per
+    session, so row s belongs to segment s.  Device tensors: ``recs`` uint8
+    [S, 4 * 160] (four records a row: the id's length as a native int32, then
+    up to 148 id bytes), ``cnt`` int32 [S] (records claimed; a reader clamps
+    it to 4) and ``stats`` int64 [8] (``_lib.AUTH_STATS``)."""
+
+    def __init__(self, S, device):
+        self.S = int(S)
+        if self.S < 1:
+            raise ValueError('AuthTable: S >= 1')
+        self.recs = torch.zeros(self.S, _lib.AUTH_K * _lib.AUTH_REC,
+                                dtype=U8, device=device)
+        self.cnt = torch.zeros(self.S, dtype=I32, device=device)
+        self.stats = torch.zeros(8, dtype=I64, device=device)
+        self.tensors = [self.recs, self.cnt, self.stats]
+
+    def clear(self, rows):
+        """Forget the identities of ``rows`` (a device int64 index tensor):
+        a connection has gone or a new one takes the row.  The counts and
+        the records are zeroed (a record is written once between two
+        clears, which the store relies on); no host read."""
+        self.cnt.index_fill_(0, rows, 0)
+        self.recs.index_fill_(0, rows, 0)
+
+    def identities(self):
+        """Per row the identities stored, as ``bytes`` (host reads: for
+        tests and tools)."""
+        cnt = self.cnt.cpu().tolist()
+        recs = self.recs.cpu().numpy()
+        out = []
+        for s in range(self.S):
+            row = []
+            for k in range(min(max(cnt[s], 0), _lib.AUTH_K)):
+                rec = recs[s, k * _lib.AUTH_REC:(k + 1) * _lib.AUTH_REC]
+                n = int(rec[:4].view('<i4')[0])
+                row.append(bytes(rec[4:4 + n]))
+            out.append(row)
+        return out
 
 
 class OrderDefer(object):
@@ -280,6 +330,7 @@ class GpuServer(object):
         self.mix_total_err = self.mix_scratch = self.mix_out = None
         # the ACL check's verdicts and counters (lazy)
         self.acl_deny = self.acl_enf = None
+        self.auth_res = self.auth_table = None
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -718,7 +769,7 @@ class GpuServer(object):
         return self.result
 
     def _serve_class(self, rx, frames, seg_table, segs, ordered, passes,
-                     defer, close, rec_off, terminate, denied):
+                     defer, close, rec_off, terminate, denied, auth=None):
         """The serve of one class of a session batch's frames through to its
         reply encode: ``frames`` with their segment table ``seg_table``
         (:meth:`_SegState.table` of ``segs``) — the whole batch
@@ -727,7 +778,9 @@ class GpuServer(object):
         ``tree_serve_ordered_sessions`` or None; ``rec_off``: where the
         encode leaves the frame starts (None: its own); ``denied``: the
         whole batch's frame count when the ACL check ran over it (its
-        fix-up goes between the serve and the encode) or None.  Returns what
+        fix-up goes between the serve and the encode) or None; ``auth``: the
+        :class:`AuthTable` when the batch's AUTH frames were served (their
+        fix-up follows the ACL check's) or None.  Returns what
         ``encode_responses`` returns."""
         L = _lib.lib()
         tree = self.tree
@@ -763,6 +816,9 @@ class GpuServer(object):
         if denied is not None:
             _lib.aclperm_fix(self.acl_deny, self.mix_cls, self.mix_sub,
                              denied, cap, r.err, self.acl_enf)
+        if auth is not None:
+            _lib.auth_fix(self.auth_res, self.mix_cls, self.mix_sub, denied,
+                          cap, r.err, auth.stats)
         enc = B.encode_responses(
             r, tree.store, self.out.numel(), out=self.out,
             presized=self.presized, terminate=terminate,
@@ -1313,6 +1369,27 @@ class GpuServer(object):
         Raises ``ValueError`` on a tree without an ACL table and when
         ``perms.addrs`` is not ``[segs.S]``.
 
+        ``perms.auth`` (an :class:`AuthTable`; None: every launch and every
+        byte are what they are with ``perms`` alone): the batch's AUTH
+        frames (opcode 100) are served (csrc/kernels/tree_auth.hip; the
+        rule: zk_auth.h).  One more launch after the segment assign takes
+        every AUTH frame of a served segment: the scheme ``digest`` with
+        credentials of at most 119 bytes stores the identity
+        ``user:base64(SHA1(credentials))`` in the segment's row — unless
+        the row holds it from an earlier batch — and is answered OK; a
+        malformed frame, any other scheme, longer credentials and a fifth
+        identity of a row are answered AUTH_FAILED (-115).  Both replies
+        are header only, with the frame's own xid; a third launch, behind
+        the ACL check's fix-up, writes the code.  The ACL check then lets a
+        ``digest`` entry grant to a connection that holds its id; ``auth``,
+        ``sasl`` and every other scheme still match nobody.  An identity
+        holds for every frame of its connection in the batch that carries
+        its AUTH frame, the frames ahead of it included.  Two equal AUTH
+        frames of one connection in one batch may take two of its four
+        slots.  A refused segment's AUTH frame stores nothing and keeps its
+        refusal; a deferred one comes back, finds its identity stored and
+        is answered OK then.  :meth:`auth_stats` reads the counters.
+
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
         tree = self.tree
@@ -1357,9 +1434,22 @@ class GpuServer(object):
         if perms is not None:
             # (before the split: a denied frame is of the serve's class)
             self._acl_enforce_buffers()
-            _lib.aclperm_check(tree.tensors, tree.acl, rx, ft.off, ft.length,
-                               ft.count, cap, sg.table(segs), perms.addrs,
-                               self.acl_deny, self.acl_enf)
+            auth = perms.auth
+            if auth is None:
+                _lib.aclperm_check(tree.tensors, tree.acl, rx, ft.off,
+                                   ft.length, ft.count, cap, sg.table(segs),
+                                   perms.addrs, self.acl_deny, self.acl_enf)
+            else:
+                if self.auth_res is None:
+                    self.auth_res = torch.zeros(cap, dtype=I32,
+                                                device=tree.device)
+                self.auth_table = auth
+                _lib.auth_frames(rx, ft.off, ft.length, ft.count, cap,
+                                 sg.table(segs), auth.tensors, self.auth_res)
+                _lib.aclperm_check_auth(
+                    tree.tensors, tree.acl, rx, ft.off, ft.length, ft.count,
+                    cap, sg.table(segs), perms.addrs, auth.tensors,
+                    self.acl_deny, self.acl_enf)
         _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
                             tree.acl is not None, self.mix_cls, self.mix_sub,
                             self.mix_foff, self.mix_flen, self.mix_counts,
@@ -1374,7 +1464,8 @@ class GpuServer(object):
         a_out, _, a_total, a_err = self._serve_class(
             rx, fa, sg.table(segs, 0), segs, ordered, passes, clip, close,
             self.mix_rec_off[0], False,
-            ft.count if perms is not None else None)
+            ft.count if perms is not None else None,
+            perms.auth if perms is not None else None)
         # the two read engines, after the batch's writes
         c_out, l_out = self.mix_scratch
         c_total, c_err = self.acl_total_err
@@ -1438,6 +1529,21 @@ class GpuServer(object):
         if self.acl_enf is None:
             return dict.fromkeys(_lib.ACLPERM_STATS, 0)
         return dict(zip(_lib.ACLPERM_STATS, self.acl_enf.cpu().tolist()))
+
+    def auth_stats(self):
+        """What the AUTH frames of ``serve_sessions_mixed(perms=
+        AclIdentity(addrs, auth=...))`` came to, from the counters of the
+        :class:`AuthTable` the last such call used (one host read): frames
+        ``ok`` and ``failed``, of the failed those that found their row
+        ``full``, of the ok those whose identity the row already held
+        (``known``), and the replies written, ``answered_ok`` and
+        ``answered_failed`` (a deferred frame is counted by the first four in
+        every batch that carries it, by the last two once).  All 0 on a
+        server that never served one."""
+        if self.auth_table is None:
+            return dict.fromkeys(_lib.AUTH_STATS, 0)
+        return dict(zip(_lib.AUTH_STATS,
+                        self.auth_table.stats.cpu().tolist()))
 
     def acl_enforce_counters(self):
         """The device counters :meth:`acl_enforce_stats` reads (int64 [8], in

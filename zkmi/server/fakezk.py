@@ -19,12 +19,16 @@ relies on:
   from getData/exists, child watches from getChildren) and trigger rules,
   including the per-session de-duplication of NodeDeleted;
 * SET_WATCHES catch-up against ``relZxid``;
+* AUTH: the ``digest`` identity is kept on the connection (nothing checks
+  it), any other scheme is answered AUTH_FAILED;
 * ensemble: several endpoints share one :class:`ZKDatabase`; stopping an
   endpoint drops its sockets but not its sessions;
 * fault hooks: refuse (stopped), accept-and-close, hang, write raw bytes,
   reply protocolVersion=1, pause reads, close/relisten on a schedule.
 """
 
+import base64
+import hashlib
 import os
 import time
 
@@ -401,6 +405,7 @@ class _ServerConn(object):
         self.sid = None
         self.handshook = False
         self.closed = False
+        self.auth_ids = []          # digest identities added with AUTH
         sock.on('data', self._on_data)
         sock.on('end', self._on_end)
         sock.on('close', self._on_close)
@@ -496,7 +501,7 @@ class _ServerConn(object):
             return
         s.last_seen = db._mono()
         try:
-            pkt = jute.decode_request(body)
+            pkt = jute.decode_request(body, auth=True)
         except (ZKDecodeError, ValueError, UnicodeDecodeError):
             self.close_from_server()
             return
@@ -508,6 +513,19 @@ class _ServerConn(object):
             db.close_session(self.sid)
             self.sock.end()
             self.server.loop.call_later(20, self.close_from_server)
+            return
+        if pkt['opcode'] == 'AUTH':
+            # DigestAuthenticationProvider: the identity stays with the
+            # connection; any other scheme fails (the connection stays open)
+            ok = pkt['scheme'] == 'digest'
+            if ok:
+                cred = pkt['auth']
+                self.auth_ids.append(
+                    cred.split(b':', 1)[0] + b':' +
+                    base64.b64encode(hashlib.sha1(cred).digest()))
+            self.write(jute.encode_response({
+                'xid': pkt['xid'], 'zxid': db.zxid, 'opcode': 'AUTH',
+                'err': 'OK' if ok else 'AUTH_FAILED'}))
             return
         rep = db.handle(pkt, self.sid)
         self.write(jute.encode_response(rep))

@@ -54,10 +54,20 @@ Known divergences from ZooKeeper:
   replies: its connections are dropped (``stats()['batches_lost']``);
 * ``enforce_acl=True``: permission and existence are those of the tree as the
   tick finds it (a node created in a tick is protected from the next one on);
-  only ``world`` and ``ip`` entries match anybody — there is no AUTH, so a
-  ``digest``, ``auth`` or ``sasl`` entry grants nothing, and no SET_ACL;
+  ``world`` and ``ip`` entries match as in ZooKeeper, and a ``digest`` entry
+  matches a connection after its AUTH (``Client.add_auth('digest',
+  b'user:password')``; csrc/kernels/zk_auth.h).  The ``auth`` and ``sasl``
+  schemes still match nobody: ZooKeeper rewrites an ``auth`` entry at CREATE
+  into the creator's identities, which is not done here.  No SET_ACL;
   GET_ACL needs no permission (ZooKeeper 3.4 / 3.5); a node whose ACL found no
-  room in the store denies every op that needs a permission.
+  room in the store denies every op that needs a permission;
+* AUTH (with ``enforce_acl``; without it an AUTH frame is answered
+  BAD_ARGUMENTS): an identity holds for every frame of its connection in the
+  tick that carries its AUTH frame, the frames ahead of the AUTH frame in the
+  stream included.  A failed AUTH (any scheme but ``digest``, a malformed
+  frame) is answered AUTH_FAILED and the connection stays open; ZooKeeper
+  closes it.  At most 4 identities a connection and credentials of at most
+  119 bytes: beyond either the answer is AUTH_FAILED.
 """
 
 import heapq
@@ -72,7 +82,8 @@ import torch
 
 from .. import consts
 from ..ops import _lib
-from .engine import AclIdentity, GpuServer, OrderDefer, SessionSegments
+from .engine import (AclIdentity, AuthTable, GpuServer, OrderDefer,
+                     SessionSegments)
 from .sessions import GpuSessionTable
 
 I64, I32, U8 = torch.int64, torch.int32, torch.uint8
@@ -178,9 +189,15 @@ class GpuZKServer(object):
                     IPv4 address, taken at ``accept`` (none for a peer that
                     is not IPv4 or IPv4-mapped: no ``ip`` entry matches it),
                     and a request its node's or parent's ACL does not allow
-                    is answered NO_AUTH.  It needs a tree with an ACL table
-                    (``ValueError`` without one) and costs two launches a
-                    tick.  Off, ACLs are stored and returned, nothing more.
+                    is answered NO_AUTH.  The server keeps an
+                    :class:`~zkmi.server.engine.AuthTable` of ``max_conns``
+                    rows: an AUTH frame with the scheme ``digest`` adds an
+                    identity to its connection, which ``digest`` entries
+                    then match; a row is forgotten when its connection
+                    closes and when a new one takes it.  It needs a tree
+                    with an ACL table (``ValueError`` without one) and costs
+                    four launches a tick.  Off, ACLs are stored and
+                    returned, nothing more.
 
     ``.port``, ``.address``, ``.servers()`` and ``.shutdown()`` as
     :class:`FakeZKServer`'s; :meth:`call` runs a function on the server's
@@ -244,7 +261,13 @@ class GpuZKServer(object):
         self.h_addrs = _pinned(S, I32, dev)
         self.np_addrs = self.h_addrs.numpy()
         self.d_addrs = torch.zeros(S, dtype=I32, device=dev)
-        self.perms = AclIdentity(self.d_addrs) if self.enforce_acl else None
+        # each row's digest identities (AUTH), and the rows to forget before
+        # the next batch: a connection has closed or a new one was accepted
+        self.auth = AuthTable(S, dev) if self.enforce_acl else None
+        self._auth_clear = set()
+        self.perms = AclIdentity(self.d_addrs, auth=self.auth) \
+            if self.enforce_acl else None
+        self.gs.auth_table = self.auth
         self._rows_dirty = True
         # -- the cut and the pack ---------------------------------------------
         self.h_raw = _pinned(self.raw_cap, U8, dev)
@@ -374,7 +397,9 @@ class GpuZKServer(object):
         was applied); with ``enforce_acl``: ``acl_denied`` (requests
         answered NO_AUTH, as of the last tick's report) — and the last batch's
         ``session_stats``, ``watch_stats``, ``resume_stats`` and
-        ``close_stats``, each read once."""
+        ``close_stats``, each read once; with ``enforce_acl`` also
+        ``auth_stats`` (``GpuServer.auth_stats``: the AUTH frames served since
+        the server started), read the same way."""
         def go():
             st = dict(self._stats)
             st['connections'] = sum(1 for c in self.rows if c is not None)
@@ -386,6 +411,8 @@ class GpuZKServer(object):
                     st[name] = getattr(self.gs, name)()
                 except ValueError:
                     st[name] = None
+            if self.enforce_acl:
+                st['auth_stats'] = self.gs.auth_stats()
             return st
         return self.call(go)
 
@@ -496,6 +523,7 @@ class GpuZKServer(object):
             c = _Conn(sock, heapq.heappop(self.free_rows))
             self.rows[c.row] = c
             self.np_addrs[c.row] = peer_ipv4(peer)
+            self._auth_clear.add(c.row)
             self._rows_dirty = True
             self.new.append(c)
             self.sel.register(sock, selectors.EVENT_READ, c)
@@ -597,6 +625,7 @@ class GpuZKServer(object):
         self.np_wslots[r] = -1
         self.np_sidx[r] = 0
         self.np_addrs[r] = 0
+        self._auth_clear.add(r)
         self._rows_dirty = True
         heapq.heappush(self.free_rows, r)
 
@@ -693,6 +722,10 @@ class GpuZKServer(object):
             self.d_sidx.copy_(self.h_sidx, non_blocking=True)
             if self.enforce_acl:
                 self.d_addrs.copy_(self.h_addrs, non_blocking=True)
+                if self._auth_clear:
+                    rows = torch.tensor(sorted(self._auth_clear), dtype=I64)
+                    self.auth.clear(rows.to(self.dev))
+                    self._auth_clear.clear()
             self._rows_dirty = False
 
     def _assemble(self, rep_off, out, err, resume, notif, close,
