@@ -257,7 +257,8 @@ PyObject* decode_reply_raw(const uint8_t* body, Py_ssize_t len,
       if (ok && o[12] == '2') ok = set_steal(d, N.stat, r.stat());
     } else if (!strcmp(o, "CREATE")) {
       ok = set_steal(d, N.path, r.ustr());
-    } else if (!strcmp(o, "EXISTS") || !strcmp(o, "SET_DATA")) {
+    } else if (!strcmp(o, "EXISTS") || !strcmp(o, "SET_DATA") ||
+               !strcmp(o, "SET_ACL")) {
       ok = set_steal(d, N.stat, r.stat());
     } else if (!strcmp(o, "GET_ACL")) {
       ok = set_steal(d, N.acl, r.acl()) && set_steal(d, N.stat, r.stat());
@@ -462,6 +463,10 @@ bool encode_request_into(PyObject* d, std::string* out, bool framed) {
       break;
     case 5:                                          // SET_DATA
       ok = w.ustr(get(d, N.path)) && w.bytes(get(d, N.data));
+      if (ok) w.i32((int32_t)as_long(get(d, N.version), -1));
+      break;
+    case 7:                                          // SET_ACL
+      ok = w.ustr(get(d, N.path)) && write_acl(w, get(d, N.acl));
       if (ok) w.i32((int32_t)as_long(get(d, N.version), -1));
       break;
     case 101: {                                      // SET_WATCHES

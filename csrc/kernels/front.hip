@@ -144,6 +144,74 @@ __global__ __launch_bounds__(FC_T) void front_cut_k(
   }
 }
 
+// front_cut_k in front of a serve that takes SET_ACL (zk_front.h
+// front_walk_setacl / front_walk_ordered_setacl: such a frame is a run of its
+// own).  Kernels of their own text: front_cut_k's two instances stay the code
+// they are.
+template <bool ORD>
+__global__ __launch_bounds__(FC_T) void front_cut_setacl_k(
+    const uint8_t* __restrict__ raw, int64_t n, int64_t raw_mis,
+    const int64_t* __restrict__ raw_starts, int64_t S, int64_t quota,
+    int64_t max_packet, const int64_t* __restrict__ fault,
+    int64_t* __restrict__ take, int32_t* __restrict__ nfr,
+    int32_t* __restrict__ flag, int32_t has_acl, int32_t* __restrict__ nwr) {
+  // (one word past the window: the high half of the last word's pair)
+  __shared__ __attribute__((aligned(16))) uint32_t win[FC_CHUNK / 4 + 4];
+  const int lane = threadIdx.x;
+  const int64_t s = blockIdx.x;
+  if (s >= S) return;
+  // the segment [a, b), clipped to the stream whatever the table holds
+  int64_t a = 0, b = 0;
+  if (*fault == 0) {
+    a = raw_starts[s];
+    b = raw_starts[s + 1];
+    if (a < 0) a = 0;
+    if (b > n) b = n;
+    if (b < a) b = a;
+  }
+  FrontCut c{0, 0, 0};
+  int32_t wr = 0;                        // (ORD)
+  if (b - a >= 4) {                      // (else: the wave leaves at once)
+    // everything of the walk is wave-uniform: the window's base included
+    int64_t wb = -((int64_t)1 << 62);    // no window yet
+    auto rd = [&](int64_t p) -> int32_t {
+      const int64_t q = a + p;           // [q, q + 4) lies inside [a, b)
+      if (q < wb || q + 4 > wb + FC_CHUNK) {
+        __syncthreads();                 // the reads of the old window are done
+        wb = ((q + raw_mis) & ~(int64_t)15) - raw_mis;
+#pragma unroll
+        for (int u = 0; u < FC_U; ++u) {
+          const int k = lane + u * FC_T;
+          *reinterpret_cast<uint4*>(&win[4 * k]) =
+              fc_fetch(raw, wb + 16 * (int64_t)k, b);
+        }
+        __syncthreads();
+      }
+      const uint32_t r = (uint32_t)(q - wb);
+      const uint32_t i = r >> 2;
+      const uint64_t two = ((uint64_t)win[i + 1] << 32) | win[i];
+      // (every lane read the same word: as a scalar the walk's state stays in
+      // SGPRs and its branches are the scalar unit's)
+      return __builtin_amdgcn_readfirstlane(
+          (int32_t)bswap32((uint32_t)(two >> (8 * (r & 3)))));
+    };
+    if (ORD) {
+      const FrontCutOrd o =
+          front_walk_ordered_setacl(b - a, quota, max_packet, has_acl != 0, rd);
+      c.take = o.take, c.nfr = o.nfr, c.flag = o.flag;
+      wr = o.nwr;
+    } else {
+      c = front_walk_setacl(b - a, quota, max_packet, rd);
+    }
+  }
+  if (lane == 0) {
+    take[s] = c.take;
+    nfr[s] = c.nfr;
+    flag[s] = c.flag;
+    if (ORD) nwr[s] = wr;
+  }
+}
+
 // The streams a gather reads.
 struct FrontSrc {
   const uint8_t* p[FRONT_PIECES];
@@ -289,20 +357,30 @@ int64_t zk_front_chunk(void) { return zk::FC_CHUNK; }
 // and fault[1] (1: the table is unsound; then every take is 0).
 // mode 0: front_walk.  mode 1: front_walk_ordered, with has_acl (the tree
 // keeps an ACL table: GET_ACL is of the ACL engine's class) -> nwr[S] too, the
-// write frames taken (mode 0 takes nwr null and leaves it alone).
+// write frames taken (mode 0 takes nwr null and leaves it alone).  mode 2 /
+// mode 3: modes 0 / 1 in front of a serve that takes SET_ACL (zk_front.h
+// front_walk_setacl / front_walk_ordered_setacl).
 int zk_front_cut_mode(const uint8_t* raw, int64_t n, const int64_t* raw_starts,
                       int64_t S, int64_t quota, int64_t max_packet,
                       int32_t mode, int32_t has_acl, int64_t* take,
                       int32_t* nfr, int32_t* flag, int32_t* nwr,
                       int64_t* fault, hipStream_t st) {
   if (S < 1 || S > 0x7fffffff || n < 0 || max_packet < 0 || mode < 0 ||
-      mode > 1 || (mode == 1 && nwr == nullptr))
+      mode > 3 || ((mode & 1) && nwr == nullptr))
     return (int)hipErrorInvalidValue;
   if (hipMemsetAsync(fault, 0, sizeof(int64_t), st) != hipSuccess) return -4;
   zk::front_table_k<<<zk::fg_blocks(S + 1), zk::FG_T, 0, st>>>(raw_starts, S,
                                                                n, fault);
   ZK_LAUNCH_CHECK();
-  if (mode == 1)
+  if (mode == 3)
+    zk::front_cut_setacl_k<true><<<(unsigned)S, zk::FC_T, 0, st>>>(
+        raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota,
+        max_packet, fault, take, nfr, flag, has_acl, nwr);
+  else if (mode == 2)
+    zk::front_cut_setacl_k<false><<<(unsigned)S, zk::FC_T, 0, st>>>(
+        raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota,
+        max_packet, fault, take, nfr, flag, 0, nullptr);
+  else if (mode == 1)
     zk::front_cut_k<true><<<(unsigned)S, zk::FC_T, 0, st>>>(
         raw, n, (int64_t)((uintptr_t)raw & 15), raw_starts, S, quota,
         max_packet, fault, take, nfr, flag, has_acl, nwr);

@@ -3,6 +3,7 @@
 // serve (the tree: zk_tree.h).
 #include "zk_acl.h"
 #include "zk_sess.h"
+#include "zk_setacl_dev.h"
 
 namespace zk {
 
@@ -530,6 +531,65 @@ int zk_tree_acl_get_sessions(const ZkTree* t, const ZkAclTable* a,
   const zk::SegTable M{g->f_seg, nullptr, g->seg_state, g->bad, g->S};
   return acl_get_launch(t, a, rx, foff, flen, n_dev, ncap, &M, ws, ws_bytes,
                         out, out_cap, rec_off, total, err, terminate, st);
+}
+
+// zk_tree_acl_get_sessions for a caller that serves SET_ACL (opcode 7; the
+// split sent those frames here: zk_tree_mix_split_setacl).  The SET_ACL pass
+// (tree_setacl.hip) runs over the class's frame table first, so a GET_ACL of
+// the batch sees the new ACL; then the class is sized, the pass's frames put
+// into their rows, and the one scan and one reply stream carry both ops in
+// request order.  addrs (null: no ADMIN check) / au (null: no identities):
+// the peers of the S segments; passes: the rounds a node; claim[claim_n]: the
+// per-node claim words, all SETACL_IDLE between calls (claim_n >= the node
+// capacity); stats[8] += the pass's counters; sws: zk_tree_setacl_workspace.
+// A batch of the class without a SET_ACL frame produces the bytes
+// zk_tree_acl_get_sessions produces.  No host read.
+int zk_tree_acl_setacl_sessions(
+    const ZkTree* t, const ZkAclTable* a, const uint8_t* rx, int64_t rx_len,
+    const int64_t* foff, const int32_t* flen, const int64_t* n_dev,
+    int64_t ncap, const ZkSegs* g, const int32_t* addrs,
+    const ZkAuthTable* au, int32_t passes, int32_t* claim, int64_t claim_n,
+    int64_t* stats, uint8_t* ws, int64_t ws_bytes, uint8_t* sws,
+    int64_t sws_bytes, uint8_t* out, int64_t out_cap, int64_t* rec_off,
+    int64_t* total, int32_t* err, int32_t terminate, hipStream_t st) {
+  if (g == nullptr || g->f_seg == nullptr || g->seg_state == nullptr ||
+      g->bad == nullptr || g->S < 1 || rx_len < 0 || passes < 0 ||
+      passes > 64 || claim == nullptr || stats == nullptr)
+    return -1;
+  if (au != nullptr && (addrs == nullptr || au->recs == nullptr ||
+                        au->cnt == nullptr || au->S < g->S))
+    return -1;
+  const zk::SegTable M{g->f_seg, nullptr, g->seg_state, g->bad, g->S};
+  if (ncap <= 0)
+    return acl_get_launch(t, a, rx, foff, flen, n_dev, ncap, &M, ws, ws_bytes,
+                          out, out_cap, rec_off, total, err, terminate, st);
+  if (out_cap < 0 || !acl_table_ok(a) ||
+      ncap >= (int64_t)0x7fffffff / zk::ACL_GROUP)
+    return -1;
+  if (claim_n < a->cap || claim_n < t->store.cap) return -1;
+  if (ws_bytes < zk_tree_acl_workspace(ncap) || ((uintptr_t)ws & 15) ||
+      sws_bytes < zk::setacl_layout(ncap, nullptr, nullptr) ||
+      ((uintptr_t)sws & 15))
+    return -1;
+  zk::AclWs w;
+  acl_layout(ncap, ws, &w);
+  zk::SetAclWs sw;
+  zk::setacl_layout(ncap, sws, &sw);
+  int rc = zk::setacl_pass(*t, *a, rx, rx_len, foff, flen, n_dev, ncap, M,
+                           addrs, au, passes, claim, sw, stats, st);
+  if (rc) return rc;
+  const unsigned nb = (unsigned)((ncap + zk::TR_T - 1) / zk::TR_T);
+  zk::acl_size_sess_k<<<nb, zk::TR_T, 0, st>>>(*t, *a, rx, foff, flen, n_dev,
+                                               ncap, w, M);
+  ZK_LAUNCH_CHECK();
+  const zk::SetAclRows rows{w.xid, w.err, w.word, w.nslot, w.sizes, w.ctr};
+  rc = zk::setacl_rows(n_dev, ncap, sw, rows, stats, st);
+  if (rc) return rc;
+  rc = zk_scan_excl_i64(w.sizes, rec_off, ncap, total, w.scan, st);
+  if (rc) return rc;
+  zk::acl_total_k<<<1, 1, 0, st>>>(total, out_cap, err, terminate, out, w);
+  ZK_LAUNCH_CHECK();
+  return zk::setacl_write(*t, *a, n_dev, ncap, sw, rows, rec_off, out, st);
 }
 
 }  // extern "C"

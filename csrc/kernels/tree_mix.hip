@@ -86,6 +86,32 @@ __global__ __launch_bounds__(MX_T) void mix_class_k(
     hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
 }
 
+// mix_class_k under the second rule (zk_mix.h mix_class_setacl: opcode 7 to
+// the ACL engine's class).  A kernel of its own text, so that mix_class_k
+// stays the code it is for every caller that does not serve SET_ACL.
+__global__ __launch_bounds__(MX_T) void mix_class_setacl_k(
+    const uint8_t* __restrict__ rx, const int64_t* __restrict__ foff,
+    const int32_t* __restrict__ flen, const int64_t* __restrict__ n_dev,
+    int64_t ncap, int32_t has_acl, int32_t* __restrict__ cls,
+    int64_t* __restrict__ hist) {
+  __shared__ int32_t h[MIX_CLASSES];
+  if (threadIdx.x < MIX_CLASSES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * MX_T + threadIdx.x;
+  int32_t c = -1;
+  if (i < ncap && i < *n_dev)
+    c = mix_class_setacl(rx, foff[i], flen[i], has_acl != 0);
+  if (i < ncap) cls[i] = c;
+#pragma unroll
+  for (int32_t k = 0; k < MIX_CLASSES; ++k) {
+    const uint64_t m = __ballot(c == k);
+    if ((threadIdx.x & 63) == 0 && m != 0) atomicAdd(&h[k], __popcll(m));
+  }
+  __syncthreads();
+  if (threadIdx.x < MIX_CLASSES)
+    hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
+}
+
 // base: the exclusive scan of hist in class-major order (class c's run of
 // block b starts at base[c * nblk + b], the class itself at base[c * nblk]).
 __global__ __launch_bounds__(MX_T) void mix_scatter_k(
@@ -366,11 +392,13 @@ int64_t zk_tree_mix_split_workspace(int64_t ncap) {
 // engine class: cls[ncap] (-1 past *n_dev), sub[ncap] (the frame's index in
 // its class), the compacted tables foff_c / flen_c ([3][ncap], class c's at
 // c * ncap) and counts[3].  Stable.  has_acl: the tree keeps an ACL table.
-int zk_tree_mix_split(const uint8_t* rx, const int64_t* foff,
-                      const int32_t* flen, const int64_t* n_dev, int64_t ncap,
-                      int32_t has_acl, int32_t* cls, int32_t* sub,
-                      int64_t* foff_c, int32_t* flen_c, int64_t* counts,
-                      uint8_t* ws, int64_t ws_bytes, hipStream_t st) {
+// setacl: the second rule (zk_mix.h mix_class_setacl), the same launches.
+static int mix_split_launch(const uint8_t* rx, const int64_t* foff,
+                            const int32_t* flen, const int64_t* n_dev,
+                            int64_t ncap, int32_t has_acl, int32_t setacl,
+                            int32_t* cls, int32_t* sub, int64_t* foff_c,
+                            int32_t* flen_c, int64_t* counts, uint8_t* ws,
+                            int64_t ws_bytes, hipStream_t st) {
   if (ncap <= 0)
     return hipMemsetAsync(counts, 0, sizeof(int64_t) * zk::MIX_CLASSES, st) !=
                    hipSuccess ? -4 : 0;
@@ -383,8 +411,12 @@ int zk_tree_mix_split(const uint8_t* rx, const int64_t* foff,
   int64_t* base = hist + m;
   int64_t* total = hist + 2 * m;
   int64_t* sws = hist + 2 * m + 8;
-  zk::mix_class_k<<<(unsigned)nblk, zk::MX_T, 0, st>>>(
-      rx, foff, flen, n_dev, ncap, has_acl, cls, hist);
+  if (setacl)
+    zk::mix_class_setacl_k<<<(unsigned)nblk, zk::MX_T, 0, st>>>(
+        rx, foff, flen, n_dev, ncap, has_acl, cls, hist);
+  else
+    zk::mix_class_k<<<(unsigned)nblk, zk::MX_T, 0, st>>>(
+        rx, foff, flen, n_dev, ncap, has_acl, cls, hist);
   ZK_LAUNCH_CHECK();
   const int rc = zk_scan_excl_i64(hist, base, m, total, sws, st);
   if (rc) return rc;
@@ -392,6 +424,27 @@ int zk_tree_mix_split(const uint8_t* rx, const int64_t* foff,
       foff, flen, ncap, cls, base, total, sub, foff_c, flen_c, counts);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+int zk_tree_mix_split(const uint8_t* rx, const int64_t* foff,
+                      const int32_t* flen, const int64_t* n_dev, int64_t ncap,
+                      int32_t has_acl, int32_t* cls, int32_t* sub,
+                      int64_t* foff_c, int32_t* flen_c, int64_t* counts,
+                      uint8_t* ws, int64_t ws_bytes, hipStream_t st) {
+  return mix_split_launch(rx, foff, flen, n_dev, ncap, has_acl, 0, cls, sub,
+                          foff_c, flen_c, counts, ws, ws_bytes, st);
+}
+
+// zk_tree_mix_split for a caller that serves SET_ACL: opcode 7 goes to the
+// ACL engine's class (on a tree with an ACL table).
+int zk_tree_mix_split_setacl(const uint8_t* rx, const int64_t* foff,
+                             const int32_t* flen, const int64_t* n_dev,
+                             int64_t ncap, int32_t has_acl, int32_t* cls,
+                             int32_t* sub, int64_t* foff_c, int32_t* flen_c,
+                             int64_t* counts, uint8_t* ws, int64_t ws_bytes,
+                             hipStream_t st) {
+  return mix_split_launch(rx, foff, flen, n_dev, ncap, has_acl, 1, cls, sub,
+                          foff_c, flen_c, counts, ws, ws_bytes, st);
 }
 
 static int64_t mix_merge_layout(int64_t ncap, uint8_t* ws, zk::MixWs* w) {

@@ -421,6 +421,12 @@ int zk_tree_mix_split(const uint8_t*, const int64_t*, const int32_t*,
                       const int64_t*, int64_t, int32_t, int32_t*, int32_t*,
                       int64_t*, int32_t*, int64_t*, uint8_t*, int64_t,
                       hipStream_t);
+// zk_tree_mix_split under the second rule (zk_mix.h mix_class_setacl): opcode
+// 7 goes to the ACL engine's class on a tree with an ACL table.
+int zk_tree_mix_split_setacl(const uint8_t*, const int64_t*, const int32_t*,
+                             const int64_t*, int64_t, int32_t, int32_t*,
+                             int32_t*, int64_t*, int32_t*, int64_t*, uint8_t*,
+                             int64_t, hipStream_t);
 int64_t zk_tree_mix_merge_workspace(int64_t ncap);
 int zk_tree_mix_merge(const int32_t*, const int32_t*, const int64_t*,
                       const int64_t*, int64_t, const uint8_t* const*,
@@ -544,6 +550,21 @@ int zk_tree_acl_get_sessions(const ZkTree*, const ZkAclTable*,
                              const int64_t*, int64_t, const ZkSegs*,
                              uint8_t*, int64_t, uint8_t*, int64_t, int64_t*,
                              int64_t*, int32_t*, int32_t, hipStream_t);
+// SET_ACL in a session batch (tree_setacl.hip; the rule: zk_setacl.h).
+// zk_tree_acl_setacl_sessions: zk_tree_acl_get_sessions with rx's length
+// after rx and, after the segment table, the peers' addresses [S] (null: no
+// ADMIN check), their identities (null: none), the rounds a node, the claim
+// words + their count (all 0x7fffffff between calls), stats[8], and behind
+// the ACL engine's workspace the pass's own (zk_tree_setacl_workspace bytes).
+int64_t zk_tree_setacl_workspace(int64_t ncap);
+int zk_tree_acl_setacl_sessions(const ZkTree*, const ZkAclTable*,
+                                const uint8_t*, int64_t, const int64_t*,
+                                const int32_t*, const int64_t*, int64_t,
+                                const ZkSegs*, const int32_t*,
+                                const ZkAuthTable*, int32_t, int32_t*, int64_t,
+                                int64_t*, uint8_t*, int64_t, uint8_t*, int64_t,
+                                uint8_t*, int64_t, int64_t*, int64_t*,
+                                int32_t*, int32_t, hipStream_t);
 // The SET_WATCHES catch-up of a session batch (tree_resume.hip; the rules:
 // zk_resume.h), after its serve: (tree, rx, its length, frames off / len,
 // count, ncap, the segment table, workspace, ecap) -> the

@@ -121,6 +121,67 @@ ZK_HD FrontCutOrd front_walk_ordered(int64_t len, int64_t quota,
   return c;
 }
 
+// ---- the cuts in front of a serve that takes SET_ACL ---------------------------
+// The SET_ACL pass (tree_setacl.hip) runs behind the serve's class and in
+// front of the batch's GET_ACL frames, whatever the order a connection sent
+// them in.  So a SET_ACL frame (judged by its opcode word, as a write is) is
+// taken only as the first frame of a connection's run and ends the run behind
+// itself, in the plain and in the ordered cut: a connection's GET_ACL sent
+// before its SET_ACL is answered from the old ACL, one sent after from the new,
+// a tick apart.  The walks are front_walk and front_walk_ordered otherwise;
+// nwr does not count a SET_ACL frame.
+template <class Rd>
+ZK_HD FrontCut front_walk_setacl(int64_t len, int64_t quota,
+                                 int64_t max_packet, Rd&& rd) {
+  FrontCut c{0, 0, 0};
+  if (quota > 0x7fffffff) quota = 0x7fffffff;
+  int64_t p = 0;
+  while (c.nfr < quota && len - p >= 4) {
+    const int32_t L = rd(p);
+    if (L < 0 || L > max_packet) {
+      c.flag = 1;
+      break;
+    }
+    if (L > len - p - 4) break;                    // the body is not whole yet
+    const int32_t op = L >= 8 ? rd(p + 8) : 0;     // (0 is no opcode)
+    const bool wr = front_is_write(op) || op == OP_SET_ACL;
+    if (wr && c.nfr > 0) break;
+    p += 4 + (int64_t)L;
+    ++c.nfr;
+    if (wr) break;
+  }
+  c.take = p;
+  return c;
+}
+
+template <class Rd>
+ZK_HD FrontCutOrd front_walk_ordered_setacl(int64_t len, int64_t quota,
+                                            int64_t max_packet, bool has_acl,
+                                            Rd&& rd) {
+  FrontCutOrd c{0, 0, 0, 0};
+  if (quota > 0x7fffffff) quota = 0x7fffffff;
+  int64_t p = 0;
+  int32_t phase = 0;
+  while (c.nfr < quota && len - p >= 4) {
+    const int32_t L = rd(p);
+    if (L < 0 || L > max_packet) {
+      c.flag = 1;
+      break;
+    }
+    if (L > len - p - 4) break;                    // the body is not whole yet
+    const int32_t op = L >= 8 ? rd(p + 8) : 0;     // (0 is no opcode)
+    if (op == OP_SET_ACL && c.nfr > 0) break;
+    if (phase == 1 && front_is_tree_write(op)) break;
+    if (front_is_late(op, has_acl)) phase = 1;
+    p += 4 + (int64_t)L;
+    ++c.nfr;
+    if (front_is_write(op)) ++c.nwr;
+    if (op == OP_CLOSE_SESSION || op == OP_SET_ACL) break;
+  }
+  c.take = p;
+  return c;
+}
+
 // What boundary s (0..S) of raw_starts[S + 1] adds to the table-fault word on
 // its own: a table that does not begin at 0, a descending pair, a boundary
 // outside [0, n].  raw_starts is read at s and, for s < S, s + 1 only.

@@ -25,4 +25,15 @@ ZK_HD int32_t mix_class(const uint8_t* __restrict__ buf, int64_t base,
   return MIX_A;
 }
 
+// The second rule, for a caller that serves SET_ACL
+// (GpuServer.serve_sessions_mixed with setacl): mix_class, but opcode 7 is of
+// the ACL engine's class on a tree with an ACL table, whatever stands behind
+// the opcode word (the pass there answers a truncated frame).  Without an ACL
+// table it stays with the serve.
+ZK_HD int32_t mix_class_setacl(const uint8_t* __restrict__ buf, int64_t base,
+                               int64_t L, bool has_acl) {
+  if (L >= 8 && has_acl && ld_be32(buf + base + 4) == OP_SET_ACL) return MIX_C;
+  return mix_class(buf, base, L, has_acl);
+}
+
 }  // namespace zk

@@ -1563,6 +1563,74 @@ void tree_acl_get_sessions(const std::vector<Tensor>& t,
          "tree_acl_get_sessions");
 }
 
+// SET_ACL in a session batch (tree_setacl.hip): tree_acl_get_sessions with
+// the SET_ACL pass in front.  addrs: [] (no ADMIN check) or [int32 [S]];
+// auth: [] or the identity table's tensors (needs addrs); claim: int32, one
+// word a node, all 0x7fffffff between calls; stats: int64 [8]; sws:
+// tree_setacl_workspace(ncap) bytes.
+int64_t tree_setacl_workspace(int64_t n) {
+  TORCH_CHECK(n >= 0, "zkmi: tree_setacl_workspace n");
+  return zk_tree_setacl_workspace(n);
+}
+
+ZkAuthTable auth_table(const std::vector<Tensor>& v, const Tensor* r);
+
+void tree_acl_setacl_sessions(
+    const std::vector<Tensor>& t, const std::vector<Tensor>& acl,
+    const Tensor& rx, const Tensor& foff, const Tensor& flen,
+    const Tensor& n_dev, int64_t ncap, const std::vector<Tensor>& sg,
+    const std::vector<Tensor>& addrs, const std::vector<Tensor>& auth,
+    int64_t passes, const Tensor& claim, const Tensor& stats, const Tensor& ws,
+    const Tensor& sws, const Tensor& out, int64_t out_cap,
+    const Tensor& rec_off, const Tensor& total, const Tensor& err,
+    bool terminate) {
+  ZkTree s = tree(t);
+  const Tensor* d = &t[0];
+  ZkAclTable a = acl_table(acl, d);
+  const ZkSegs m = segs(sg, ncap, d);
+  TORCH_CHECK(a.cap >= s.store.cap, "zkmi: acl.node_acl has ", a.cap,
+              " elements, needs ", s.store.cap);
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 28), "zkmi: tree_acl ncap");
+  TORCH_CHECK(out_cap >= 0, "zkmi: tree_acl_setacl_sessions out_cap");
+  TORCH_CHECK(passes >= 0 && passes <= 64,
+              "zkmi: tree_acl_setacl_sessions passes 0 .. 64");
+  TORCH_CHECK(addrs.size() <= 1, "zkmi: addrs is [] or one tensor");
+  TORCH_CHECK(auth.empty() || !addrs.empty(),
+              "zkmi: an auth table needs the peers' addresses");
+  const int32_t* ad = nullptr;
+  if (!addrs.empty()) {
+    TORCH_CHECK(addrs[0].numel() == m.S, "zkmi: addrs has ", addrs[0].numel(),
+                " entries, sessions ", m.S);
+    ad = P<int32_t>(addrs[0], I32, m.S, "addrs", d);
+  }
+  ZkAuthTable au;
+  if (!auth.empty()) {
+    au = auth_table(auth, d);
+    TORCH_CHECK(au.S >= m.S, "zkmi: the auth table has ", au.S,
+                " rows, sessions ", m.S);
+  }
+  const int64_t nodes = a.cap > s.store.cap ? a.cap : s.store.cap;
+  uint8_t* sw = P<uint8_t>(sws, U8, zk_tree_setacl_workspace(ncap),
+                           "setacl workspace", d);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(sw) % 16 == 0,
+              "zkmi: setacl workspace must be 16-byte aligned");
+  hip_ok(zk_tree_acl_setacl_sessions(
+             &s, &a, P<uint8_t>(rx, U8, 1, "rx", d), rx.numel(),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, &m, ad,
+             auth.empty() ? nullptr : &au, (int32_t)passes,
+             P<int32_t>(claim, I32, nodes, "claim", d), claim.numel(),
+             P<int64_t>(stats, I64, 8, "stats", d), acl_ws(ws, ncap, d),
+             ws.numel(), sw, sws.numel(),
+             P<uint8_t>(out, U8, out_cap, "out", d), out_cap,
+             P<int64_t>(rec_off, I64, ncap, "rec_off", d),
+             P<int64_t>(total, I64, 1, "total", d),
+             P<int32_t>(err, I32, 1, "err", d), terminate ? 1 : 0,
+             cur_stream()),
+         "tree_acl_setacl_sessions");
+}
+
 // Mixed batches (tree_mix.hip): the split of a batch's frame table by engine
 // class and the merge of the engines' reply streams into request order.
 int64_t tree_mix_split_workspace(int64_t n) {
@@ -1606,6 +1674,31 @@ void tree_mix_split(const Tensor& rx, const Tensor& foff, const Tensor& flen,
              mix_ws(ws, zk_tree_mix_split_workspace(ncap), d), ws.numel(),
              cur_stream()),
          "tree_mix_split");
+}
+
+// tree_mix_split for a caller that serves SET_ACL: opcode 7 is of the ACL
+// engine's class
+void tree_mix_split_setacl(const Tensor& rx, const Tensor& foff,
+                           const Tensor& flen, const Tensor& n_dev,
+                           int64_t ncap, bool has_acl, const Tensor& cls,
+                           const Tensor& sub, const Tensor& foff_c,
+                           const Tensor& flen_c, const Tensor& counts,
+                           const Tensor& ws) {
+  const Tensor* d = &rx;
+  TORCH_CHECK(ncap >= 0 && ncap < (1ll << 31) - 1, "zkmi: tree_mix ncap");
+  hip_ok(zk_tree_mix_split_setacl(
+             P<uint8_t>(rx, U8, 1, "rx"),
+             P<int64_t>(foff, I64, ncap, "frame_off", d),
+             P<int32_t>(flen, I32, ncap, "frame_len", d),
+             P<int64_t>(n_dev, I64, 1, "count", d), ncap, has_acl ? 1 : 0,
+             P<int32_t>(cls, I32, ncap, "cls", d),
+             P<int32_t>(sub, I32, ncap, "sub", d),
+             P<int64_t>(foff_c, I64, 3 * ncap, "frame_off_c", d),
+             P<int32_t>(flen_c, I32, 3 * ncap, "frame_len_c", d),
+             P<int64_t>(counts, I64, 3, "counts", d),
+             mix_ws(ws, zk_tree_mix_split_workspace(ncap), d), ws.numel(),
+             cur_stream()),
+         "tree_mix_split_setacl");
 }
 
 // streams / rec_offs / totals / errs: one tensor per class (serve, GET_ACL,
@@ -2168,9 +2261,9 @@ void front_cut(const Tensor& raw, int64_t n, const Tensor& raw_starts,
                const Tensor& nfr, const Tensor& flag, const Tensor& fault,
                int64_t mode, bool has_acl, const c10::optional<Tensor>& nwr) {
   const Tensor* d = &raw;
-  TORCH_CHECK(mode == 0 || mode == 1, "zkmi: front_cut mode is 0 or 1");
-  TORCH_CHECK(mode == 0 || (nwr.has_value() && nwr->defined()),
-              "zkmi: front_cut mode 1 writes nwr");
+  TORCH_CHECK(mode >= 0 && mode <= 3, "zkmi: front_cut mode is 0 .. 3");
+  TORCH_CHECK((mode & 1) == 0 || (nwr.has_value() && nwr->defined()),
+              "zkmi: front_cut modes 1 and 3 write nwr");
   const int64_t S = raw_starts.numel() - 1;
   TORCH_CHECK(S >= 1 && S < (1ll << 31) - 1,
               "zkmi: a segment table has at least one segment");
@@ -2195,7 +2288,7 @@ void front_cut(const Tensor& raw, int64_t n, const Tensor& raw_starts,
              P<int64_t>(take, I64, S, "take", d),
              P<int32_t>(nfr, I32, S, "nfr", d),
              P<int32_t>(flag, I32, S, "flag", d),
-             P<int32_t>(*nwr, I32, S, "nwr", d),
+             (mode & 1) ? P<int32_t>(*nwr, I32, S, "nwr", d) : nullptr,
              P<int64_t>(fault, I64, 1, "fault", d), cur_stream()),
          "front_cut");
 }
@@ -2433,6 +2526,11 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor count, int ncap, bool has_acl, Tensor(a!) cls, "
         "Tensor(b!) sub, Tensor(c!) frame_off_c, Tensor(d!) frame_len_c, "
         "Tensor(e!) counts, Tensor(f!) ws) -> ()", &tree_mix_split);
+  m.def("tree_mix_split_setacl(Tensor rx, Tensor frame_off, "
+        "Tensor frame_len, Tensor count, int ncap, bool has_acl, "
+        "Tensor(a!) cls, Tensor(b!) sub, Tensor(c!) frame_off_c, "
+        "Tensor(d!) frame_len_c, Tensor(e!) counts, Tensor(f!) ws) -> ()",
+        &tree_mix_split_setacl);
   m.def("tree_mix_merge(Tensor cls, Tensor sub, Tensor count, Tensor counts, "
         "int ncap, Tensor[] streams, Tensor[] rec_offs, Tensor[] totals, "
         "Tensor[] errs, Tensor(a!) out, int out_cap, Tensor(b!) rec_off, "
@@ -2453,6 +2551,14 @@ TORCH_LIBRARY(zkmi, m) {
         "Tensor[] segs, Tensor(a!) ws, Tensor(b!) out, int out_cap, "
         "Tensor(c!) rec_off, Tensor(d!) total, Tensor(e!) err, "
         "bool terminate=False) -> ()", &tree_acl_get_sessions);
+  m.def("tree_setacl_workspace(int n) -> int", &tree_setacl_workspace);
+  m.def("tree_acl_setacl_sessions(Tensor(a!)[] tree, Tensor(b!)[] acl, "
+        "Tensor rx, Tensor frame_off, Tensor frame_len, Tensor count, "
+        "int ncap, Tensor[] segs, Tensor[] addrs, Tensor[] auth, int passes, "
+        "Tensor(c!) claim, Tensor(d!) stats, Tensor(e!) ws, Tensor(f!) sws, "
+        "Tensor(g!) out, int out_cap, Tensor(h!) rec_off, Tensor(i!) total, "
+        "Tensor(j!) err, bool terminate=False) -> ()",
+        &tree_acl_setacl_sessions);
   m.def("watch_events(Tensor r_op, Tensor r_err, Tensor count, int ncap, "
         "Tensor fired, Tensor(a!) bsum, Tensor(b!) ev_slot, "
         "Tensor(c!) ev_type, Tensor(d!) ev_path_off, Tensor(e!) ev_path_len, "

@@ -29,7 +29,16 @@ tree as built every node carries the open ACL: the check's fast path.
 ``--acl-vector`` first binds every node to one three-entry vector whose last
 entry grants (a digest entry, an ip entry of another network, world:anyone):
 every check walks the arena's bytes; nothing is denied either way, so all
-sides still produce the same reply bytes."""
+sides still produce the same reply bytes.
+
+``--setacl``: the cost of the SET_ACL pass (csrc/kernels/tree_setacl.hip) on
+the sessions_mixed side alone, ``--runs`` runs a variant (a run: a captured
+graph, the median of ``--reps`` replays): ``off`` (``setacl=False``: the
+launches of the call without the argument, the number to hold against the
+parent commit's ``--side new``), ``on, none`` (``setacl=True``, no SET_ACL
+frame in the batch) and ``on, one a connection`` (every connection's first
+frame is a SET_ACL of a leaf of its own with version -1, so every replay
+applies it again)."""
 
 import argparse
 import os
@@ -106,6 +115,57 @@ def connection(rng, r, nodes, fanout, data):
     return b''.join(out), lists
 
 
+def setacl_frame(xid, path):
+    """A SET_ACL of ``path`` to the open ACL, any version."""
+    vec = struct.pack('>iii', 1, 31, 5) + b'world' + \
+        struct.pack('>i', 6) + b'anyone'
+    body = struct.pack('>iii', xid, consts.OP_CODES['SET_ACL'], len(path)) + \
+        path + vec + struct.pack('>i', -1)
+    return struct.pack('>i', len(body)) + body
+
+
+def setacl_variants(tree, S, r, a, dev, conns, sids, slots, out_cap, perms):
+    """--setacl: the three variants, ``a.runs`` runs each."""
+    def batch(parts):
+        cuts = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
+        return (dev_bytes(b''.join(parts), dev), int(cuts[-1]),
+                SessionSegments(torch.tensor(cuts, dtype=I64, device=dev),
+                                torch.tensor(sids, dtype=I64, device=dev),
+                                torch.tensor(slots, dtype=I32, device=dev)))
+    plain = [c[0] for c in conns]
+    withset = []
+    for s_, p in enumerate(plain):
+        first = 4 + struct.unpack_from('>i', p, 0)[0]
+        v = (s_ * 977) % a.nodes
+        withset.append(setacl_frame(
+            1, b'/bench/d%06d/n%09d' % (v // a.fanout, v)) + p[first:])
+    srv = GpuServer(tree, S * r, out_cap, seq_order=False)
+    print('S %5d x r %6d = %7d requests' % (S, r, S * r), flush=True)
+    for name, parts, kw in (
+            ('off', plain, {}),
+            ('on, none', plain, {'setacl': True}),
+            ('on, one a connection', withset, {'setacl': True})):
+        rx, n, segs = batch(parts)
+        _, total, err, ft = srv.serve_sessions_mixed(rx, n, segs, perms=perms,
+                                                     **kw)
+        torch.cuda.synchronize()
+        assert int(err.item()) == 0 and int(ft.count.item()) == S * r
+        meds = []
+        for _ in range(a.runs):
+            g = graph_of(lambda: srv.serve_sessions_mixed(
+                rx, n, segs, perms=perms, **kw))
+            meds.append(timed(g.replay, a.reps)[0])
+            del g
+        print('  %-22s %s us  (range %.1f .. %.1f, reply %.2f MB)' % (
+            name, ' '.join('%.1f' % m for m in meds), min(meds), max(meds),
+            int(total.item()) / 1e6), flush=True)
+    st = srv.setacl_stats()
+    assert st['applied'] > 0 and st['unreached'] == 0 and \
+        st['store_full'] == 0, st
+    del srv
+    torch.cuda.empty_cache()
+
+
 def bind_vector(tree):
     """Every node's ACL word -> one three-entry vector, its bytes put on
     the store's arena top (the intern index is not told: no CREATE of the
@@ -143,13 +203,17 @@ def shape(tree, S, r, a, dev):
                            torch.tensor(sids, dtype=I64, device=dev),
                            torch.tensor(slots, dtype=I32, device=dev))
     out_cap = S * r * 256 + sum(c[1] for c in conns) * per_list + (1 << 16)
-    one = GpuServer(tree, S * r, out_cap, seq_order=False)
     perms = None
     if a.enforce_acl:
         # 10.1.x.y, a connection an address
         perms = AclIdentity(torch.tensor(
             [0x0A010000 + (s & 0xFFFF) for s in range(S)], dtype=I32,
             device=dev))
+    if a.setacl:
+        setacl_variants(tree, S, r, a, dev, conns, sids, slots, out_cap,
+                        perms)
+        return
+    one = GpuServer(tree, S * r, out_cap, seq_order=False)
     _, total, err, ft = one.serve_sessions_mixed(rx, n, segs, perms=perms)
     torch.cuda.synchronize()
     T = int(total.item())
@@ -227,6 +291,10 @@ def main():
                     help='serve the sessions_mixed side with perms=')
     ap.add_argument('--acl-vector', action='store_true',
                     help='every node carries a three-entry ACL vector')
+    ap.add_argument('--setacl', action='store_true',
+                    help='the SET_ACL pass: off / on without / on with one '
+                    'SET_ACL a connection, --runs runs each')
+    ap.add_argument('--runs', type=int, default=5)
     a = ap.parse_args()
     shapes = SHAPES if not a.shape else \
         [tuple(int(x) for x in s.split('x')) for s in a.shape]

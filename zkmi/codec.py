@@ -15,7 +15,14 @@ from . import jute
 IMPL = 'python'
 
 encode_request = jute.encode_request
-decode_response = jute.decode_response
+
+
+def decode_response(body, xid_map):
+    """:func:`zkmi.jute.decode_response` as the client takes replies: a
+    SET_ACL reply included (the native decoder decodes it too)."""
+    return jute.decode_response(body, xid_map, set_acl=True)
+
+
 encode_connect_request = jute.encode_connect_request
 decode_connect_response = jute.decode_connect_response
 decode_connect_request = jute.decode_connect_request

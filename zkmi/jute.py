@@ -405,6 +405,11 @@ def encode_request(pkt):
         w.write_ustring(pkt['path'])
         w.write_buffer(pkt.get('data', b''))
         w.write_int(pkt.get('version', -1))
+    elif op == 'SET_ACL':
+        # SetACLRequest {ustring path; vector<ACL> acl; int version}
+        w.write_ustring(pkt['path'])
+        w.write_acl(pkt.get('acl', []))
+        w.write_int(pkt.get('version', -1))
     elif op == 'SET_WATCHES':
         w.write_long(pkt['relZxid'])
         ev = pkt['events']
@@ -423,13 +428,15 @@ def encode_request(pkt):
     return w.getvalue()
 
 
-def decode_request(body, auth=False):
+def decode_request(body, auth=False, set_acl=False):
     """Server-mode request decode (``zk-buffer.js:58-95``, ``:138-253``).
     ``auth``: an AUTH request is decoded too (type, scheme, auth).  Off, it
     is an unsupported opcode, as it is for the GPU server's request parse
     (csrc/kernels/zk_wire.h parse_request), whose oracle this function is:
     there AUTH frames are served by a pass of their own
-    (csrc/kernels/zk_auth.h auth_frame)."""
+    (csrc/kernels/zk_auth.h auth_frame).  ``set_acl``: the same for a SET_ACL
+    request (path, acl, version; the pass: csrc/kernels/zk_setacl.h
+    setacl_frame)."""
     r = JuteReader(body)
     pkt = {}
     pkt['xid'] = r.read_int()
@@ -453,6 +460,10 @@ def decode_request(body, auth=False):
         pkt['path'] = r.read_ustring()
         pkt['data'] = r.read_buffer()
         pkt['version'] = r.read_int()
+    elif op == 'SET_ACL' and set_acl:
+        pkt['path'] = r.read_ustring()
+        pkt['acl'] = r.read_acl()
+        pkt['version'] = r.read_int()
     elif op == 'SET_WATCHES':
         pkt['relZxid'] = r.read_long()
         pkt['events'] = {
@@ -475,10 +486,14 @@ def decode_request(body, auth=False):
 # Responses (client decode, server encode)
 # --------------------------------------------------------------------------
 
-def decode_response(body, xid_map):
+def decode_response(body, xid_map, set_acl=False):
     """Reply header + body, resolving the opcode from the special-xid table or
     the xid->opcode map recorded at encode time (``zk-buffer.js:275-331``).
-    The body is decoded only when ``err == 'OK'`` (``:292``)."""
+    The body is decoded only when ``err == 'OK'`` (``:292``).  ``set_acl``:
+    a SET_ACL reply is decoded too (its Stat).  Off, it is an unsupported
+    opcode, as it is for the GPU reply decoders (csrc/kernels/decode.hip),
+    whose oracle this function is; the client's codec (zkmi/codec.py) decodes
+    it."""
     r = JuteReader(body)
     if r.end < 16:
         raise ZKDecodeError('reply shorter than its 16-byte header')
@@ -500,7 +515,7 @@ def decode_response(body, xid_map):
             pkt['stat'] = r.read_stat()
     elif op == 'CREATE':
         pkt['path'] = r.read_ustring()
-    elif op in ('EXISTS', 'SET_DATA'):
+    elif op in ('EXISTS', 'SET_DATA') or (op == 'SET_ACL' and set_acl):
         pkt['stat'] = r.read_stat()
     elif op == 'GET_ACL':
         pkt['acl'] = r.read_acl()
@@ -539,7 +554,7 @@ def encode_response(pkt):
             w.write_stat(pkt['stat'])
     elif op == 'CREATE':
         w.write_ustring(pkt['path'])
-    elif op in ('EXISTS', 'SET_DATA'):
+    elif op in ('EXISTS', 'SET_DATA', 'SET_ACL'):
         w.write_stat(pkt['stat'])
     elif op == 'GET_ACL':
         w.write_acl(pkt['acl'])

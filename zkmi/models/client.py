@@ -526,6 +526,27 @@ class Client(FSM):
 
     get_acl = getACL
 
+    def setACL(self, path, acl, version, cb):
+        """Replace the node's ACL.  ``acl`` has the shape ``create`` takes
+        in ``options['acl']``; ``version`` is the expected ``aversion``
+        (``None`` or -1: any).  ``cb(None, stat)`` with the node's Stat
+        after the change, or ``cb(ZKError)`` with code ``NO_NODE``,
+        ``NO_AUTH`` (ADMIN on the node is needed), ``BAD_VERSION`` or
+        ``INVALID_ACL`` (an empty list).  Not in the reference client."""
+        _check_str(path, 'path')
+        if not isinstance(acl, list) or \
+                not all(isinstance(a, dict) for a in acl):
+            raise TypeError('acl ([object]) is required')
+        _check_int(version, 'version', optional=True)
+        _check_func(cb)
+        if version is None:
+            version = -1
+        self._request({'opcode': 'SET_ACL', 'path': path,
+                       'acl': [dict(a) for a in acl], 'version': version},
+                      cb, lambda pkt: cb(None, pkt['stat']))
+
+    set_acl = setACL
+
     def sync(self, path, cb):
         _check_str(path, 'path')
         _check_func(cb)

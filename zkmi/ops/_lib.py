@@ -249,6 +249,17 @@ def tree_mix_split(rx, frame_off, frame_len, count, ncap, has_acl, cls, sub,
                          counts, ws)
 
 
+def tree_mix_split_setacl(rx, frame_off, frame_len, count, ncap, has_acl, cls,
+                          sub, frame_off_c, frame_len_c, counts, ws):
+    """:func:`tree_mix_split` for a caller that serves SET_ACL: a frame with
+    opcode 7 is of the ACL engine's class (1) on a tree with an ACL table
+    (zk_mix.h mix_class_setacl); every other frame as there.  The same
+    launches."""
+    lib().tree_mix_split_setacl(rx, frame_off, frame_len, count, int(ncap),
+                                bool(has_acl), cls, sub, frame_off_c,
+                                frame_len_c, counts, ws)
+
+
 def tree_mix_merge(cls, sub, count, counts, ncap, streams, rec_offs, totals,
                    errs, out, out_cap, rec_off, total, err, ws,
                    terminate=False):
@@ -405,6 +416,39 @@ def tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count, ncap,
     lib().tree_acl_get_sessions(tree, acl, rx, frame_off, frame_len, count,
                                 int(ncap), list(segs), ws, out, int(out_cap),
                                 rec_off, total, err, bool(terminate))
+
+
+# SET_ACL in a session batch (csrc/kernels/tree_setacl.hip; the rule:
+# zk_setacl.h).  What GpuServer.setacl_stats reports, in the order of the
+# kernels' counters, and the idle value of a node's claim word
+SETACL_STATS = ('applied', 'bad_version', 'denied', 'invalid', 'unreached',
+                'store_full')
+SETACL_IDLE = 0x7fffffff
+
+
+def tree_setacl_workspace(ncap):
+    """Bytes of the SET_ACL pass's workspace for ``ncap`` frames (a uint8
+    tensor; nothing in it needs zeroing)."""
+    return lib().tree_setacl_workspace(int(ncap))
+
+
+def tree_acl_setacl_sessions(tree, acl, rx, frame_off, frame_len, count, ncap,
+                             segs, addrs, auth, passes, claim, stats, ws, sws,
+                             out, out_cap, rec_off, total, err,
+                             terminate=False):
+    """:func:`tree_acl_get_sessions` for a class that carries SET_ACL frames
+    (:func:`tree_mix_split_setacl`): the SET_ACL pass first — judge, intern,
+    ``passes`` rounds a node —, then GET_ACL and SET_ACL replies in one
+    stream in request order.  ``addrs`` (int32 [S]; None: ADMIN is not
+    checked), ``auth`` (the identity table's tensors or None), ``claim``
+    (int32, a word a node, all ``SETACL_IDLE`` between calls), ``stats``
+    (int64 [8], accumulated, ``SETACL_STATS``), ``sws``
+    (:func:`tree_setacl_workspace` bytes).  No host read."""
+    lib().tree_acl_setacl_sessions(
+        tree, list(acl), rx, frame_off, frame_len, count, int(ncap),
+        list(segs), [] if addrs is None else [addrs],
+        [] if auth is None else list(auth), int(passes), claim, stats, ws,
+        sws, out, int(out_cap), rec_off, total, err, bool(terminate))
 
 
 # the SET_WATCHES catch-up of a session batch (csrc/kernels/tree_resume.hip;
@@ -607,7 +651,12 @@ def front_cut(raw, n, raw_starts, quota, max_packet, take, nfr, flag, fault,
     one GET_ACL is of the serve's class) or SET_WATCHES frame, and which a
     CLOSE_SESSION ends after itself.  ``nwr`` (int32 [S], required): the
     write frames taken.  ``mode=0`` launches what the call without the
-    keywords does and leaves ``nwr`` alone."""
+    keywords does and leaves ``nwr`` alone.
+
+    ``mode=2`` / ``mode=3``: modes 0 / 1 in front of a serve that takes
+    SET_ACL (zk_front.h front_walk_setacl / front_walk_ordered_setacl): a
+    SET_ACL frame is taken only as the first frame of a run and ends the run
+    behind itself; ``nwr`` does not count it."""
     if mode == 0:
         lib().front_cut(raw, int(n), raw_starts, int(quota), int(max_packet),
                         take, nfr, flag, fault)

@@ -331,6 +331,8 @@ class GpuServer(object):
         # the ACL check's verdicts and counters (lazy)
         self.acl_deny = self.acl_enf = None
         self.auth_res = self.auth_table = None
+        # the SET_ACL pass's claim words, counters and workspace (lazy)
+        self.setacl_claim = self.setacl_ctr = self.setacl_ws = None
         if tree.watch is not None:
             self._init_watch(cap_frames, dev)
 
@@ -1239,7 +1241,8 @@ class GpuServer(object):
     def serve_sessions_mixed(self, rx, n, segs, terminate=False, table=None,
                              max_frame=None, out=None, resume=False,
                              close=False, ordered=False, passes=4,
-                             defer=None, perms=None):
+                             defer=None, perms=None, setacl=False,
+                             setacl_passes=4):
         """Serve ``rx[:n]``, the concatenated whole frames of the ``segs.S``
         connections of :class:`SessionSegments` ``segs``, whatever ops they
         mix, as ONE batch: :meth:`serve_sessions` for every op of
@@ -1390,9 +1393,53 @@ class GpuServer(object):
         refusal; a deferred one comes back, finds its identity stored and
         is answered OK then.  :meth:`auth_stats` reads the counters.
 
+        ``setacl`` (off: the call launches what it launches without the
+        argument): the batch's SET_ACL frames (opcode 7) are served
+        (csrc/kernels/tree_setacl.hip; the rule: zk_setacl.h).  The split
+        sends them to the ACL engine's class, and a pass over that class's
+        frame table runs before its GET_ACL frames are sized — after the
+        batch's serve-class writes and after the batch's creates have had
+        their ACLs bound.  A frame is answered, in this order, BAD_ARGUMENTS
+        (a body that is no whole SET_ACL request), INVALID_ACL (an empty
+        vector, or one of 16 MiB or more), NO_NODE, NO_AUTH (with ``perms``:
+        the node's ACL does not grant ADMIN to the segment's address and,
+        with ``perms.auth``, its identities; without ``perms`` nothing is
+        checked, as nothing else is), BAD_VERSION (``version`` is neither -1
+        nor the node's ``aversion``), or OK with the node's Stat, whose
+        ``aversion`` is the one this frame produced: a frame of 4 + 84
+        bytes; every failure is header only.  The batch contract:
+
+        * ADMIN is judged on the ACL as the pass finds it: a SET_ACL of the
+          batch does not take the permission from a later one of it;
+        * on one node the batch's SET_ACLs run in frame order, whichever
+          segments they come from, one a round, ``setacl_passes`` rounds: a
+          frame its node's rounds do not reach is answered SYSTEMERROR
+          without effect (the convention of ``ordered`` and ``passes``);
+          different nodes proceed in parallel;
+        * the batch's serve-class requests were all judged (``perms``) and
+          served before any SET_ACL of it took effect, and every GET_ACL of
+          the batch sees the ACLs all its SET_ACLs leave;
+        * every frame that reached its version check takes a zxid, failed
+          ones included, unique and increasing in frame order, above those
+          of the batch's serve-class writes.
+
+        Only a frame past every check but the version has its vector
+        interned, so a client without ADMIN cannot fill the store; the
+        vector of a frame that then fails BAD_VERSION stays interned
+        (nothing in the store is reclaimed).  A vector the store has no room
+        for fails its frame with SYSTEMERROR and leaves the node's ACL as it
+        is.  No scheme or id is validated, equal entries are not removed and
+        an ``auth`` entry is stored as sent (it matches nobody), as for
+        CREATE.  A refused or deferred segment's SET_ACL frame does nothing
+        and keeps its placeholder.  :meth:`setacl_stats` reads the counters.
+        Raises ``ValueError`` on a tree without an ACL table.
+
         Raises ``ValueError`` on a ``fused_rows`` or ``read_only`` server
         and on a sharded tree, as the two entry points do."""
         tree = self.tree
+        if setacl and tree.acl is None:
+            raise ValueError('serve_sessions_mixed: setacl needs a tree '
+                             'with an ACL table (GpuTree(acl_cap=...))')
         if self.fused_rows or self.read_only:
             raise ValueError('serve_sessions_mixed: no session form of the '
                              'read-only or the fused-rows serve')
@@ -1450,10 +1497,10 @@ class GpuServer(object):
                     tree.tensors, tree.acl, rx, ft.off, ft.length, ft.count,
                     cap, sg.table(segs), perms.addrs, auth.tensors,
                     self.acl_deny, self.acl_enf)
-        _lib.tree_mix_split(rx, ft.off, ft.length, ft.count, cap,
-                            tree.acl is not None, self.mix_cls, self.mix_sub,
-                            self.mix_foff, self.mix_flen, self.mix_counts,
-                            self.mix_split_ws)
+        split = _lib.tree_mix_split_setacl if setacl else _lib.tree_mix_split
+        split(rx, ft.off, ft.length, ft.count, cap, tree.acl is not None,
+              self.mix_cls, self.mix_sub, self.mix_foff, self.mix_flen,
+              self.mix_counts, self.mix_split_ws)
         _lib.sess_split_segments(sg.f_seg, self.mix_cls, self.mix_sub,
                                  ft.count, cap, seg_c)
         fa, fc, fl = self.mix_frames
@@ -1469,7 +1516,18 @@ class GpuServer(object):
         # the two read engines, after the batch's writes
         c_out, l_out = self.mix_scratch
         c_total, c_err = self.acl_total_err
-        if tree.acl is not None:
+        if setacl:
+            self._setacl_buffers()
+            _lib.tree_acl_setacl_sessions(
+                tree.tensors, tree.acl, rx, fc.off, fc.length, fc.count, cap,
+                sg.table(segs, 1),
+                perms.addrs if perms is not None else None,
+                perms.auth.tensors if perms is not None and
+                perms.auth is not None else None,
+                setacl_passes, self.setacl_claim, self.setacl_ctr,
+                self._acl_workspace(), self.setacl_ws, c_out, c_out.numel(),
+                self.acl_rec_off, c_total, c_err, False)
+        elif tree.acl is not None:
             _lib.tree_acl_get_sessions(
                 tree.tensors, tree.acl, rx, fc.off, fc.length, fc.count, cap,
                 sg.table(segs, 1), self._acl_workspace(), c_out,
@@ -1508,6 +1566,38 @@ class GpuServer(object):
         c = acl[4].cpu().tolist()
         return (c[_lib.AC_ENT], min(c[_lib.AC_TOP], acl[1].numel()),
                 c[_lib.AC_LOST])
+
+    def _setacl_buffers(self):
+        """The SET_ACL pass's claim words (one a node, idle), counters and
+        workspace, allocated on first use."""
+        if self.setacl_claim is None:
+            dev = self.tree.device
+            # (node_acl covers the node store: the ops check it)
+            nodes = self.tree.acl[0].numel()
+            self.setacl_claim = torch.full((nodes,), _lib.SETACL_IDLE,
+                                           dtype=I32, device=dev)
+            self.setacl_ctr = torch.zeros(8, dtype=I64, device=dev)
+            self.setacl_ws = torch.empty(
+                _lib.tree_setacl_workspace(self.cap_frames), dtype=U8,
+                device=dev)
+
+    def setacl_stats(self):
+        """What the SET_ACL frames of ``serve_sessions_mixed(setacl=True)``
+        came to since the server was built (one host read): frames
+        ``applied``, refused ``bad_version``, ``denied`` (NO_AUTH),
+        ``invalid`` (INVALID_ACL), ``unreached`` (their node's rounds ran
+        out: SYSTEMERROR) and ``store_full`` (the vector found no room:
+        SYSTEMERROR).  All 0 on a server that never served one."""
+        if self.setacl_ctr is None:
+            return dict.fromkeys(_lib.SETACL_STATS, 0)
+        return dict(zip(_lib.SETACL_STATS, self.setacl_ctr.cpu().tolist()))
+
+    def setacl_counters(self):
+        """The device counters :meth:`setacl_stats` reads (int64 [8], in
+        ``_lib.SETACL_STATS`` order), for a caller that folds them into a
+        read of its own; no host read."""
+        self._setacl_buffers()
+        return self.setacl_ctr
 
     def _acl_enforce_buffers(self):
         """The ACL check's verdicts and counters, allocated on first use."""

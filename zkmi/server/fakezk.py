@@ -330,6 +330,23 @@ class ZKDatabase(object):
             raise ZKServerError('NO_NODE')
         return node.acl, node.stat
 
+    def set_acl(self, path, acl, version):
+        """SET_ACL, in this order: INVALID_ACL for an empty vector
+        (:meth:`create`'s rule), NO_NODE, BAD_VERSION against the node's
+        ``aversion``; then the ACL is replaced, ``aversion`` bumped and a
+        zxid taken.  No permission is checked here, as nowhere else."""
+        if not acl:
+            raise ZKServerError('INVALID_ACL')
+        node = self.nodes.get(path)
+        if node is None:
+            raise ZKServerError('NO_NODE')
+        if version != -1 and version != node.stat.aversion:
+            raise ZKServerError('BAD_VERSION')
+        self.zxid += 1
+        node.acl = acl
+        node.stat.aversion += 1
+        return node.stat
+
     def set_watches(self, rel, events, sid):
         for path in events.get('dataChanged', []):
             node = self.nodes.get(path)
@@ -380,6 +397,9 @@ class ZKDatabase(object):
                                             pkt['version'])
             elif op == 'GET_ACL':
                 rep['acl'], rep['stat'] = self.get_acl(pkt['path'])
+            elif op == 'SET_ACL':
+                rep['stat'] = self.set_acl(pkt['path'], pkt['acl'],
+                                           pkt['version'])
             elif op == 'SYNC':
                 pass
             elif op == 'PING':
@@ -501,7 +521,7 @@ class _ServerConn(object):
             return
         s.last_seen = db._mono()
         try:
-            pkt = jute.decode_request(body, auth=True)
+            pkt = jute.decode_request(body, auth=True, set_acl=True)
         except (ZKDecodeError, ValueError, UnicodeDecodeError):
             self.close_from_server()
             return

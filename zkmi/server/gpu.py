@@ -58,9 +58,21 @@ Known divergences from ZooKeeper:
   matches a connection after its AUTH (``Client.add_auth('digest',
   b'user:password')``; csrc/kernels/zk_auth.h).  The ``auth`` and ``sasl``
   schemes still match nobody: ZooKeeper rewrites an ``auth`` entry at CREATE
-  into the creator's identities, which is not done here.  No SET_ACL;
-  GET_ACL needs no permission (ZooKeeper 3.4 / 3.5); a node whose ACL found no
-  room in the store denies every op that needs a permission;
+  into the creator's identities, which is not done here.  GET_ACL needs no
+  permission (ZooKeeper 3.4 / 3.5); a node whose ACL found no room in the
+  store denies every op that needs a permission;
+* SET_ACL (``Client.set_acl``; served whenever the tree has an ACL table,
+  ADMIN checked with ``enforce_acl``; csrc/kernels/zk_setacl.h): a SET_ACL
+  frame is taken only as the first frame of its connection's run and ends
+  the run behind itself, so a connection's GET_ACL sent before its SET_ACL is
+  answered from the old ACL and one sent after from the new, a tick apart.
+  ADMIN is judged on the ACL as the tick's pass finds it, before any SET_ACL
+  of the tick took effect.  SET_ACLs of several connections on one node run
+  in row order, one a round, 4 rounds a tick: a fifth one of a tick is
+  answered SYSTEMERROR without effect (``stats()['setacl_unreached']``), not
+  deferred.  Equal entries are not removed and an ``auth`` entry is not
+  rewritten; the vector of a SET_ACL that fails BAD_VERSION stays in the
+  store (nothing in it is reclaimed);
 * AUTH (with ``enforce_acl``; without it an AUTH frame is answered
   BAD_ARGUMENTS): an identity holds for every frame of its connection in the
   tick that carries its AUTH frame, the frames ahead of the AUTH frame in the
@@ -299,8 +311,11 @@ class GpuZKServer(object):
         self.h_tx = _pinned(self.tx_cap, U8, dev)
         self.mv_tx = memoryview(self.h_tx.numpy())
         # (with enforce_acl one word more, the last: replies answered NO_AUTH)
+        # (on a tree with an ACL table one word before it: SET_ACL frames
+        # their node's rounds did not reach)
+        self.serve_setacl = tree.acl is not None
         self.nrep = 4 * S + 1 + (_R_NORD if P else _R_N) + \
-            (1 if self.enforce_acl else 0)
+            (1 if self.serve_setacl else 0) + (1 if self.enforce_acl else 0)
         # the ordered tick: the cut's write counts, what the serve deferred;
         # a connection advances by `used`, not by `take`
         self.d_nwr = torch.zeros(S, dtype=I32, device=dev)
@@ -325,7 +340,7 @@ class GpuZKServer(object):
              'sessions_expired', 'sessions_closed', 'handshakes',
              'host_reads', 'max_reads_per_tick', 'deferred_frames',
              'max_writes_per_tick', 'order_max_rank', 'order_scratch_full',
-             'acl_denied'),
+             'acl_denied', 'setacl_unreached'),
             0)
         self._calls = []
         self._lock = threading.Lock()
@@ -394,7 +409,10 @@ class GpuZKServer(object):
         saw; ``>= order_passes``: it deferred) and ``order_scratch_full``
         (ticks in which a snapshot found no room in the tree's scratch tail:
         the request was answered SYSTEMERROR, a SET_DATA among them after it
-        was applied); with ``enforce_acl``: ``acl_denied`` (requests
+        was applied); on a tree with an ACL table: ``setacl_unreached``
+        (SET_ACL frames answered SYSTEMERROR because their node's rounds of
+        the tick ran out, as of the last tick's report); with
+        ``enforce_acl``: ``acl_denied`` (requests
         answered NO_AUTH, as of the last tick's report) — and the last batch's
         ``session_stats``, ``watch_stats``, ``resume_stats`` and
         ``close_stats``, each read once; with ``enforce_acl`` also
@@ -824,7 +842,8 @@ class GpuZKServer(object):
         P = self.order_passes
         _lib.front_cut(self.d_raw, nup, self.d_rstarts, quota,
                        consts.MAX_PACKET, self.d_take, self.d_nfr,
-                       self.d_flag, self.d_fault, mode=1 if P else 0,
+                       self.d_flag, self.d_fault,
+                       mode=(1 if P else 0) + (2 if self.serve_setacl else 0),
                        has_acl=self.tree.acl is not None,
                        nwr=self.d_nwr if P else None)
         _lib.lib().scan_excl(self.d_take, self.d_starts, self.d_starts[S:],
@@ -835,11 +854,13 @@ class GpuZKServer(object):
             out, _, err, _ = gs.serve_sessions_mixed(
                 rx, self.d_starts[S:], self.segs, table=self.table,
                 resume=True, close=True, ordered=True, passes=P,
-                defer=self.defer, perms=self.perms)
+                defer=self.defer, perms=self.perms,
+                setacl=self.serve_setacl)
         else:
             out, _, err, _ = gs.serve_sessions_mixed(
                 rx, self.d_starts[S:], self.segs, table=self.table,
-                resume=True, close=True, perms=self.perms)
+                resume=True, close=True, perms=self.perms,
+                setacl=self.serve_setacl)
         self._assemble(gs.seg.rep_off, out, err,
                        (gs.resume_notif[0], gs.resume_slots[1]),
                        (gs.notif[0], gs.notif_slots[1]),
@@ -853,6 +874,8 @@ class GpuZKServer(object):
         if P:
             words += [self.defer.deferred, self.d_nwr.sum().reshape(1),
                       gs.order_counters()]
+        if self.serve_setacl:
+            words += [gs.setacl_counters()[4:5]]
         if self.enforce_acl:
             words += [gs.acl_enforce_counters()[3:4]]
         rep, total = self._report(words)
@@ -869,6 +892,8 @@ class GpuZKServer(object):
                                        int(words[_R_RANK]))
             if words[_R_SCRATCH] > self.tree.scratch.numel():
                 st['order_scratch_full'] += 1
+        if self.serve_setacl:                       # (the server's own sum)
+            st['setacl_unreached'] = int(words[_R_NORD if P else _R_N])
         if self.enforce_acl:
             st['acl_denied'] = int(words[-1])       # (the server's own sum)
         st['dup_slot'] += int(words[_R_DUP])
@@ -939,6 +964,7 @@ class GpuZKServer(object):
             self.d_none, self.d_none, self.d_over_tx, self.d_none,
             self.d_none, self.d_fstats[0:1], self.d_none, self.d_none] +
             [self.d_none] * ((4 if self.order_passes else 0) +
+                             (1 if self.serve_setacl else 0) +
                              (1 if self.enforce_acl else 0)))
         self._stats['expiry_passes'] += 1
         self._stats['sessions_expired'] += len(due)
